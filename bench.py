@@ -2,6 +2,8 @@
 """bench.py -- predicted frames/sec of the VPTR-NAR train step (KTH 10->10 @ 64x64) on N MI355X.
 
     python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full        # + graph verification, roofline pass, configs 2 / 4 / 5, CPU baseline
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR   # + what the last timed step computed, as DIR/*.npy
     python bench.py --gpus N ...                      # WORLD_SIZE unset: bench.py starts its N ranks itself (one per GPU), like
                                                       # the reference's mp.spawn entry point (train_NAR_mp.py:319-326)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -591,6 +593,31 @@ def _ddp_script_iter(dev, dropout):
             dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 1 << 22       # elements of the transformer's post-step state that --dump-outputs writes (16 MB of float32)
+
+
+def dump_outputs(path, out, T):
+    """--dump-outputs: what the last timed step computed, for an output-for-output comparison of two builds on the same arguments.
+    <term>.npy (float64, shape [1]): every entry of the step's result dict (loss terms, gradient norm); T_state_sample.npy (float32):
+    a fixed sample of the transformer's post-step state_dict -- every floating-point entry in state_dict order, all of a tensor of
+    <= 4096 elements, else a share of DUMP_SAMPLE proportional to its size at indices drawn from RandomState(20240 + entry number)"""
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.asarray([float(v)], dtype=np.float64))
+    sd = [(k, v) for k, v in T.state_dict().items() if v.is_floating_point()]
+    total = sum(v.numel() for _, v in sd)
+    parts = []
+    for i, (k, v) in enumerate(sd):
+        flat = v.detach().reshape(-1)
+        n = flat.numel()
+        if n > 4096:
+            m = min(n, max(4096, int(DUMP_SAMPLE * n / total)))
+            idx = np.sort(np.random.RandomState(20240 + i).randint(0, n, size=m))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(path, "T_state_sample.npy"), torch.cat(parts).numpy().astype(np.float32))
+
+
 # ---- rank start-up ------------------------------------------------------------------------------------------------------------------
 def _free_port():
     import socket
@@ -667,9 +694,16 @@ def main():
     ap.add_argument("--graph", type=int, default=int(os.environ.get("VPTR_GRAPH", "1")),
                     help="1 (default): one GPU: the whole step is one hipGraph; several ranks: forward + backward are one hipGraph, the "
                          "exchange and the optimizer stay eager (no collective is captured); 0: eager")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the ms/step lines of BASELINE configs 2 / 4 / 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: verify_graph on the captured step, the instrumented roofline pass, "
+                         "the ms/step of the other BASELINE configs, the CPU baseline and the exchange timeline.  Without it a run sets up, warms "
+                         "up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented roofline pass")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the ms/step lines of BASELINE configs 2 / 4 / 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64): its loss "
+                         "terms and gradient norm, and a fixed seeded sample of the transformer's post-step state")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default): --batch clips per GPU; strong: the reference's DistributedSampler semantics, a fixed "
                          "--global-batch split as global // world per rank (utils/dataset.py:72)")
@@ -688,6 +722,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_probe:
         _cpu_probe([int(k) for k in args.cpu_probe.split(",")], args.cpu_probe_pin, args.cpu_probe_steps)
         return
@@ -803,10 +839,11 @@ def main():
             dist.all_reduce(flag, op=dist.ReduceOp.MIN)
             if flag.item() < 0.5 and err is None:
                 err = "graph capture failed on another rank"
-        if err is None:
+        if err is None and args.full:
             try:
-                # the graph is only timed if it computes what the eager step computes: replay i vs an eager step from the same state, and a
-                # run of replays vs the eager trajectory (loss terms, gradient norm, post-step parameters); the state is restored afterwards
+                # --full: the graph is only timed if it computes what the eager step computes: replay i vs an eager step from the same state,
+                # and a run of replays vs the eager trajectory (loss terms, gradient norm, post-step parameters); the state is restored
+                # afterwards, so the timed steps start from the same state with or without the check
                 ok, graph_check = trainer.verify_graph(past, fut, steps=3, rtol=2e-3)
                 graph_check["nodes"] = trainer.graph_nodes
                 if not ok:
@@ -856,6 +893,8 @@ def main():
         allt = [torch.zeros(1, device=dev, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(allt, torch.tensor([dt_own], device=dev, dtype=torch.float64))
         per_rank = [float(x.item()) for x in allt]
+    if rank == 0 and args.dump_outputs:   # before anything else steps the trainer: `out` are the static buffers of a captured step
+        dump_outputs(args.dump_outputs, out, T)
     if comm is not None and cs:
         exp_ms = sum(a.elapsed_time(b) for a, b in cs.get("events", ())) / max(cs.get("steps", 1), 1)
         mine = torch.tensor([exp_ms, cs.get("wait_host_s", 0.0) * 1e3 / max(cs.get("steps", 1), 1)], device=dev, dtype=torch.float64)
@@ -876,31 +915,32 @@ def main():
         })
         import vptr_amd.train as _tr
         comm["dp_chunks"] = _tr.DP_CHUNKS
-        # tuning table for the first real multi-GPU run: ONE extra, untimed step with HIP events behind every
+        # --full: tuning table for the first real multi-GPU run: ONE extra, untimed step with HIP events behind every
         # weight-gradient chunk and behind every Work.wait(), per rank, in ms from the start of the exchange
-        try:
-            trainer.comm_stats = {"timeline": True}
-            trainer.step(past, fut)
-            torch.cuda.synchronize()
-            tl = trainer.comm_stats.get("last_timeline")
-            trainer.comm_stats = None
-            mine_tl = None
-            if tl is not None:
-                mine_tl = {"rank": rank, "chunk_end_ms": [round(tl["t0"].elapsed_time(e), 3) for e in tl["chunk_end"]],
-                           "bytes_released_by_chunk": tl["sent_bytes"],
-                           "allreduce_done_ms": [round(tl["t0"].elapsed_time(e), 3) for e in tl["ar_done"]], "allreduce_bytes": tl["ar_bytes"]}
-            if world > 1:
-                alltl = [None] * world
-                dist.all_gather_object(alltl, mine_tl)
-            else:
-                alltl = [mine_tl]
-            comm["exchange_timeline"] = {
-                "what": "one untimed step: HIP events on the launch stream, ms since the first weight-gradient chunk was enqueued; chunk_end = the chunk's "
-                        "GEMM finished (its slab range goes out), allreduce_done = that piece's Work.wait() passed on the launch stream",
-                "per_rank": alltl}
-        except Exception as e:  # noqa
-            trainer.comm_stats = None
-            comm["exchange_timeline"] = {"error": str(e)[:200]}
+        if args.full:
+            try:
+                trainer.comm_stats = {"timeline": True}
+                trainer.step(past, fut)
+                torch.cuda.synchronize()
+                tl = trainer.comm_stats.get("last_timeline")
+                trainer.comm_stats = None
+                mine_tl = None
+                if tl is not None:
+                    mine_tl = {"rank": rank, "chunk_end_ms": [round(tl["t0"].elapsed_time(e), 3) for e in tl["chunk_end"]],
+                               "bytes_released_by_chunk": tl["sent_bytes"],
+                               "allreduce_done_ms": [round(tl["t0"].elapsed_time(e), 3) for e in tl["ar_done"]], "allreduce_bytes": tl["ar_bytes"]}
+                if world > 1:
+                    alltl = [None] * world
+                    dist.all_gather_object(alltl, mine_tl)
+                else:
+                    alltl = [mine_tl]
+                comm["exchange_timeline"] = {
+                    "what": "one untimed step: HIP events on the launch stream, ms since the first weight-gradient chunk was enqueued; chunk_end = the chunk's "
+                            "GEMM finished (its slab range goes out), allreduce_done = that piece's Work.wait() passed on the launch stream",
+                    "per_rank": alltl}
+            except Exception as e:  # noqa
+                trainer.comm_stats = None
+                comm["exchange_timeline"] = {"error": str(e)[:200]}
         if world > 1 and comm["allreduce_bytes_per_step"] > 0:   # ring all-reduce moves 2 (n - 1) / n of the payload over each rank's links
             comm["bus_GBps_if_fully_exposed"] = None if comm["exposed_comm_ms_per_step"]["max"] <= 0 else round(
                 comm["allreduce_bytes_per_step"] * 2.0 * (world - 1) / world / (comm["exposed_comm_ms_per_step"]["max"] * 1e-3) / 1e9, 1)
@@ -934,7 +974,7 @@ def main():
         if comm is not None:
             res["comm"] = comm
             res["rccl_ranks"] = comm["rccl_ranks"] if comm["backend"] == "nccl" else 0
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 trainer._graph = trainer._front = None  # instrumented eager pass
                 trainer.world = 1      # rank 0 alone runs it: no collective may be issued (the other ranks are at the final barrier)
@@ -955,12 +995,12 @@ def main():
             except Exception as e:  # noqa
                 res["roofline"] = {"bound": "mfma", "achieved": None, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": None,
                                    "traffic": None, "error": str(e)[:200]}
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             trainer.opt.close()
             del trainer
             torch.cuda.empty_cache()
             res["other_configs"] = other_configs(dev, args.dropout, skip=(args.config,))
-        if world == 1 and not args.no_cpu_baseline and args.config == "k64":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "k64":
             res["cpu_baseline"] = cpu_baseline()
         print(json.dumps(res))
         sys.stdout.flush()

@@ -11,7 +11,10 @@ What it does
   3. saves inputs, expected outputs and expected gradients as .npz (tiny configs: full tensors;
      full-size K64 config: per-tensor L2 norms + 2048 sampled elements).
 
-Fixtures are data only (arrays + JSON strings); no reference source or pickled reference objects.
+Fixtures are data only (arrays + JSON strings); no reference source or pickled reference objects -- with one
+exception: ckpt_ref_nar24.tar is a checkpoint file as the reference's save_ckpt writes it (tensors, a loss history of
+utils.train_summary.Loss_tuple instances; its embedded source-tree copy stubbed out), because reading such a file is
+what the checkpoint-interchange test checks.
 """
 import json
 import os
@@ -605,6 +608,31 @@ def pos_case(ref, name):
     np.savez_compressed(os.path.join(GOLD, name + ".npz"), **save)
 
 
+def ckpt_case(ref, name, seed):
+    """a checkpoint file written by the reference's own save_ckpt (utils/train_summary.py:130-147): a small VPTRFormerNAR
+    (d 24, 4 heads, 1 + 1 layers, filled with `seed`), an un-stepped AdamW, a one-entry loss history, epoch 2.  The writer's
+    `read_code_files` is stubbed to {} for this one call, so the file carries no copy of the reference's source tree under
+    'code' -- only tensors, the loss history and the pickle globals the reference's load_ckpt resolves.
+    -> tests/golden/<name>.tar (tests/test_cpu.py::test_checkpoint_interop_with_reference)"""
+    import shutil
+    import tempfile
+    import utils.train_summary as RS
+    Tr = ref.VPTRFormerNAR(2, 2, 8, 8, 24, 4, 1, 1, 0.0, 4, 4, False, True)
+    fill.apply_fill(Tr, seed)
+    opt = torch.optim.AdamW(Tr.parameters(), lr=1e-4)
+    ld = RS.init_loss_dict(["T_MSE"])
+    ld["T_MSE"].val.append(0.25)
+    code, RS.read_code_files = RS.read_code_files, lambda: {}
+    tmp = tempfile.mkdtemp()
+    try:
+        RS.save_ckpt({"VPTR_Transformer": Tr}, {"optimizer_T": opt}, 2, ld, tmp)
+        shutil.copyfile(os.path.join(tmp, "epoch_2.tar"), os.path.join(GOLD, name + ".tar"))
+    finally:
+        RS.read_code_files = code
+        shutil.rmtree(tmp, ignore_errors=True)
+    print(f"[{name}] reference checkpoint written ({os.path.getsize(os.path.join(GOLD, name + '.tar'))} bytes)")
+
+
 def main():
     """python oracle/make_golden.py [fixture names ...]   (no names: regenerate every fixture)"""
     os.makedirs(GOLD, exist_ok=True)
@@ -667,6 +695,8 @@ def main():
                                                            padding_type="zero", out_layer="Tanh", norm="bair", sample=1024)),
         ("step_kth128_n2_digest", lambda n: step_case(ref, n, dict(k64, Tf=40, H=16, W=16, window_size=8), 528, 128, 2, 108, steps=2,
                                                        sample=1024)),
+        # a checkpoint the reference itself wrote (the checkpoint-interchange test reads it instead of importing the reference)
+        ("ckpt_ref_nar24", lambda n: ckpt_case(ref, n, 5)),
     ]
     only = sys.argv[1:]
     for name, fn in cases:

@@ -25,8 +25,8 @@ def _run(extra, timeout=900):
     import signal
     attempt_s, last = 300, None
     for attempt in range(3):
-        p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                              "--no-other-configs"] + extra, env=dict(env, VPTR_BENCH_HANG_DUMP_S=str(attempt_s - 30)), stdout=subprocess.PIPE,
+        p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+                              "--no-cpu-baseline", "--no-other-configs"] + extra, env=dict(env, VPTR_BENCH_HANG_DUMP_S=str(attempt_s - 30)), stdout=subprocess.PIPE,
                              stderr=subprocess.PIPE, text=True, start_new_session=True)
         try:
             out, err = p.communicate(timeout=min(attempt_s, timeout))
@@ -95,3 +95,34 @@ def test_rank_failure_is_loud():
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_plain_run_dumps_outputs(tmp_path):
+    """a plain one-GPU run (no --full) prints the headline line only -- the timed path, none of the --full extras -- and
+    --dump-outputs writes what its last timed step computed: the loss terms the line reports and a sample of the post-step
+    transformer state, float32 / float64, within 64 MB"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "VPTR_BENCH_SHARE_GPU")}
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+                        "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 2 and res["warmup"] == 1 and res["n_gpus"] == 1 and res["loss_sane"], res
+    assert res["ms_per_step"] > 0 and abs(res["value"] - 2 * 10 / res["ms_per_step"] * 1e3) <= 1e-3 * res["value"] + 0.5
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in res, k
+    for k in ("roofline", "other_configs", "cpu_baseline"):
+        assert k not in res, k
+    assert res["graph_check"] is None and res["config"]["launch"] == "hipGraph"
+    files = sorted(os.listdir(d))
+    assert set(files) >= {"T_total.npy", "T_GDL.npy", "T_MSE.npy", "T_bpc.npy", "grad_norm.npy", "T_state_sample.npy"}, files
+    assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+    for f in files:
+        a = np.load(d / f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
+    for k, v in res["final_terms"].items():
+        assert abs(float(np.load(d / (k + ".npy"))[0]) - v) <= 1e-6 * abs(v) + 1e-6, k
+    assert np.load(d / "T_state_sample.npy").size > 1 << 20

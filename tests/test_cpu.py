@@ -266,29 +266,48 @@ def test_checkpoint_roundtrip_and_ddp_prefix(tmp_path):
     assert start == 3 and torch.equal(T3.state_dict()["frame_queries"], T.state_dict()["frame_queries"])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference checkout (build container only)")
+def _pickle_globals(f):
+    """the (module, name) globals the data.pkl of a torch.save zip file references -- what an unpickler has to resolve"""
+    import pickletools
+    import zipfile
+    z = zipfile.ZipFile(f)
+    raw = z.read([n for n in z.namelist() if n.endswith("data.pkl")][0])
+    return {tuple(arg.split(" ", 1)) for op, arg, _ in pickletools.genops(raw) if op.name == "GLOBAL"}
+
+
 def test_checkpoint_interop_with_reference(tmp_path):
-    """a checkpoint written by the REFERENCE's save_ckpt loads here, and one written here loads through its load_ckpt"""
-    from oracle.ref_import import import_reference
+    """a checkpoint written by the REFERENCE's save_ckpt (tests/golden/ckpt_ref_nar24.tar, oracle/make_golden.py::ckpt_case) loads
+    here, and one written here loads through the reference's load_ckpt: a bare torch.load that resolves only globals a reference-written
+    file holds, with the same top-level layout and a state dict of the same keys, shapes and dtypes"""
+    import vptr_amd.model as M
     from vptr_amd import checkpoint as C
-    ref = import_reference()
-    import utils.train_summary as RS  # the reference's own module
-    Tr = ref.VPTRFormerNAR(2, 2, 8, 8, 48, 8, 1, 1, 0.0, 4, 4, False, True)
-    fill.apply_fill(Tr, 5)
-    optr = torch.optim.AdamW(Tr.parameters(), lr=1e-4)
-    ld = RS.init_loss_dict(["T_MSE"])
-    ld["T_MSE"].val.append(0.25)
-    RS.save_ckpt({"VPTR_Transformer": Tr}, {"optimizer_T": optr}, 2, ld, tmp_path / "ref")
-    _, T = _tiny_modules()
-    loss_dict, start = C.resume_training({"VPTR_Transformer": T}, {}, tmp_path / "ref" / "epoch_2.tar", ["T_MSE"])
+    ref_file = os.path.join(ROOT, "tests", "golden", "ckpt_ref_nar24.tar")
+
+    def tiny():
+        return M.VPTRFormerNAR(2, 2, 8, 8, 24, 4, 1, 1, 0.0, 4, 4, False, True)
+    Tr = tiny()
+    fill.apply_fill(Tr, 5)      # the fill the reference's module got before its save_ckpt
+    T = tiny()
+    loss_dict, start = C.resume_training({"VPTR_Transformer": T}, {}, ref_file, ["T_MSE"])
     assert start == 2 and loss_dict["T_MSE"].val == [0.25]
     for (k, a), (k2, b) in zip(Tr.state_dict().items(), T.state_dict().items()):
         assert k == k2 and torch.equal(a, b), k
     f = C.save_ckpt({"VPTR_Transformer": T}, {}, 4, loss_dict, tmp_path / "ours")
-    # what the reference's load_ckpt does (train_summary.py:150-160); torch >= 2.6 needs weights_only=False for its pickled class
-    ck = torch.load(f, map_location=None, weights_only=False)
-    assert ck["epoch"] == 4 and isinstance(ck["loss_dict"]["T_MSE"], RS.Loss_tuple) and ck["loss_dict"]["T_MSE"].val == [0.25]
-    Tr.load_state_dict(ck["Module_state_dict"]["VPTR_Transformer"])
+    # what the reference's load_ckpt does (train_summary.py:150-160) is a plain torch.load: every global of this file must be one that a
+    # file the reference wrote references too (utils.train_summary.Loss_tuple, torch storages, OrderedDict), nothing of vptr_amd
+    want = _pickle_globals(ref_file)
+    assert ("utils.train_summary", "Loss_tuple") in want
+    assert _pickle_globals(f) <= want, _pickle_globals(f) - want
+    assert ("utils.train_summary", "Loss_tuple") in _pickle_globals(f)
+    ck, rk = C.load_ckpt(f), C.load_ckpt(ref_file)
+    assert ck[2] == 4 and ck[3]["T_MSE"].val == [0.25]
+    ours, theirs = ck[0]["VPTR_Transformer"], rk[0]["VPTR_Transformer"]
+    assert [(k, tuple(v.shape), v.dtype) for k, v in ours.items()] == [(k, tuple(v.shape), v.dtype) for k, v in theirs.items()]
+    # the reference's Module.load_state_dict on that state dict: the same tensors come back
+    T2 = tiny()
+    T2.load_state_dict(ours)
+    for (k, a), (_, b) in zip(T2.state_dict().items(), Tr.state_dict().items()):
+        assert torch.equal(a, b), k
 
 
 def test_flat_adamw_state_dict_is_torch_adamw_compatible():
@@ -508,6 +527,15 @@ def test_bench_refuses_fewer_devices_than_asked():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0"],
                        env=dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "does not match WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+def test_bench_refuses_zero_timed_steps():
+    """--steps sets the number of timed steps, and ms_per_step is measured over them: a run with none is refused before any set-up"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0", "--warmup", "0"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be >= 1" in (r.stderr + r.stdout)
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
 @pytest.mark.parametrize("rows_mode", [128, 256, 192])

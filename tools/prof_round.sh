@@ -6,7 +6,7 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 R=${R:-r06}; export R
 OUT=gpurun_out/$R; mkdir -p $OUT; rm -rf $OUT/stats $OUT/pmc $OUT/rccl
-BENCH="python bench.py --graph 0 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs"   # eager launches: one traced kernel per launch
+BENCH="python bench.py --graph 0 --steps 20 --warmup 5 --full --no-cpu-baseline --no-other-configs"   # eager launches: one traced kernel per launch
 SHORT="python bench.py --graph 0 --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-other-configs"
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o b --output-format csv -- $BENCH > $OUT/bench_stdout.log 2>&1
 tail -1 $OUT/bench_stdout.log > $OUT/bench_line.json
@@ -15,11 +15,11 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc -o w --output-format csv -
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES -d $OUT/pmc -o m1 --output-format csv -- $SHORT > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $OUT/pmc -o m2 --output-format csv -- $SHORT > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM -d $OUT/pmc -o m3 --output-format csv -- $SHORT > /dev/null 2>&1
-XCH="python bench.py --force-exchange --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-other-configs"   # the multi-rank code path: 4 plain weight-gradient chunks
+XCH="python bench.py --force-exchange --steps 2 --warmup 1 --full --no-cpu-baseline --no-roofline --no-other-configs"   # the multi-rank code path: 4 plain weight-gradient chunks
 rm -rf $OUT/pmcx
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmcx -o f --output-format csv -- $XCH > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmcx -o w --output-format csv -- $XCH > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats -d $OUT/rccl -o r --output-format csv -- python bench.py --force-exchange --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-other-configs > $OUT/rccl_stdout.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/rccl -o r --output-format csv -- python bench.py --force-exchange --steps 5 --warmup 2 --full --no-cpu-baseline --no-roofline --no-other-configs > $OUT/rccl_stdout.log 2>&1
 python - <<'PY'
 import csv, collections, json, glob, os
 R = os.environ.get("R", "r03")
@@ -36,7 +36,7 @@ steps = 28.0   # 5 warm-up + 20 timed + 3 instrumented
 tot = sum(float(r["TotalDurationNs"]) for r in rows) / 1e6 / steps
 gemm = sum(float(r["TotalDurationNs"]) for r in rows if "gemm" in r["Name"] or "conv_planes" in r["Name"] or "wgrad" in r["Name"]) / 1e6 / steps
 with open(OUT + "/%s_bench_kernel_stats.md" % R, "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --graph 0 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs   (eager, N=16, bf16x3, dropout 0.1;\n")
+    f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --graph 0 --steps 20 --warmup 5 --full --no-cpu-baseline --no-other-configs   (eager, N=16, bf16x3, dropout 0.1;\n")
     f.write("# 5 warm-up + 20 timed + 3 instrumented steps = 28 steps; per-step figures = totals / 28)\n")
     f.write("# kernel time %.1f ms/step: MFMA GEMM kernels %.1f, everything else %.1f\n\n" % (tot, gemm, tot - gemm))
     f.write("| kernel | calls/step | ms/step | avg us | % |\n|---|---|---|---|---|\n")

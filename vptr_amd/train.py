@@ -465,15 +465,17 @@ class NARTrainer:
         return self._step_impl(past, future)
 
     @staticmethod
-    def _warm_up_for_capture(warmup, step):
+    def _warm_up_for_capture(warmup, step, any_rank=None):
         """eager steps in front of a capture: `warmup` - 1 of them, then as many more as the tile-row tuning of the grouped weight-gradient
         launches still wants (ops.wgrad_tune_open: each setting is timed ops._TUNE_SAMPLES times, the first, cold sample not counted), then
         the geometry is FIXED (ops.wgrad_tune_settle) and one last step issues exactly the launches -- and table uploads, counted in
-        ops._upload_stats -- the capture will issue."""
+        ops._upload_stats -- the capture will issue.  Whether a timing has been booked depends on how far this host runs ahead of its
+        GPU, so with several ranks (`any_rank`: True if the flag holds on any rank) every rank takes the same number of extra steps: each
+        of them issues the step's all-reduces, and a rank that stopped early would pair its next collective with another rank's step."""
         for _ in range(max(warmup, 1) - 1):
             step()
         extra = 0
-        while ops.wgrad_tune_open() and extra < 2 * ops._TUNE_SAMPLES:
+        while extra < 2 * ops._TUNE_SAMPLES and (any_rank(ops.wgrad_tune_open()) if any_rank else ops.wgrad_tune_open()):
             step()
             extra += 1
         ops.wgrad_tune_settle()
@@ -528,7 +530,7 @@ class NARTrainer:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self._warm_up_for_capture(warmup, lambda: self._step_impl(self._static_past, self._static_future))
+            self._warm_up_for_capture(warmup, lambda: self._step_impl(self._static_past, self._static_future), self._any_rank)
         torch.cuda.current_stream().wait_stream(s)
         ops.reserve_graph_staging(count=ops._upload_stats["count"] + 4, nbytes=max(1 << 16, 2 * ops._upload_stats["max_bytes"]))
         ops.wgrad_tune_settle()
@@ -549,6 +551,14 @@ class NARTrainer:
         g.instantiate()
         self._front = g
         return g
+
+    def _any_rank(self, flag):
+        """`flag` or-reduced over the process group (MAX all-reduce of one element on the launch stream)"""
+        if self.pg is None or self.world == 1:
+            return bool(flag)
+        t = torch.tensor([1.0 if flag else 0.0], device=self.opt.flat.device)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX, group=self.pg)
+        return t.item() > 0.5
 
     def _front_impl(self, past, future):
         """`_step_impl` up to the end of the backward pass: weight gradients recorded but not launched, no collective, no optimizer"""
