@@ -51,7 +51,7 @@ int vptr_wgrad_sync_stats(int* out_dev, vptr_stream_t stream);
  * work (a second trainer on another stream, weight-gradient chunks beside RCCL kernels or beside a main-stream backward pass) pass
  * split_k >= 0 and get the plain grouped launch, which has no shared state.  Breaking the contract cannot hang or corrupt results
  * (destination adds are atomic, every wait is bounded) -- it costs bounded-spin time-outs, visible in vptr_wgrad_sync_stats.
- * The A/B switches of INTEGRATION.md's table (VPTR_GEMM_*, VPTR_WGRAD_*, VPTR_NORM_*, VPTR_DWCONV_GEN) are read ONCE, at the first launch
+ * The A/B switches of INTEGRATION.md's table (VPTR_WGRAD_SYNC, VPTR_NORM_*, VPTR_LN_*, VPTR_DWCONV_GEN, ...) are read ONCE, at the first launch
  * that consults them; VPTR_ATTN16 / VPTR_ATTN_MFMA / VPTR_ATTN16_FWD1 are read per launch (the tests switch attention families inside
  * one process). */
 
@@ -253,7 +253,7 @@ int vptr_gemm_tile_cols(int N);
  *      1   plain launch, 128 x 176 tiles, two workgroups per CU
  *     -1   panel-synchronous persistent launch, 128 x 176 tiles (needs equal token counts and >= 1024 tiles; see the contract above)
  *     -2 / -3   256 x 176 tiles, one workgroup per CU (1.47x the flops per staged operand byte): persistent (>= 512 tiles) / plain
- *     -4 / -5   192 x 176 tiles, three stages, one workgroup per CU: persistent / plain (measured slower; tools/rejected/README.md)
+ *     < -3      rejected
  * vptr_amd.ops.plan_wgrad_launches is the worked example of cutting a backward pass's problems into such launches. */
 int vptr_gemm_grouped(const vptr_gemm_desc* proto, const vptr_gemm_desc* descs_dev, const int* tile_start_dev, int count,
                       int total_tiles, vptr_stream_t stream);

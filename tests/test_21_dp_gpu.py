@@ -47,7 +47,7 @@ def _worker(rank, world, port, q, G=4, full=True):
         # eight processes on ONE GPU oversubscribe its hardware queues; the scheduler then time-slices them with wave save / restore, under which
         # a queue intermittently aborts with HSA_STATUS_ERROR_ILLEGAL_INSTRUCTION (4 of 8 runs, profiles/r06_dp8_repeat.log) -- an artefact of
         # sharing the device that one-process-per-GPU jobs do not have.  One hardware queue per process keeps the total under the limit.
-        if os.environ.get("VPTR_TEST_KEEP_HW_QUEUES") != "1":   # (tools/r06_lease19.sh measures the failure rate without it)
+        if os.environ.get("VPTR_TEST_KEEP_HW_QUEUES") != "1":   # (profiles/r06_dp8_hwq_ab.log: the failure rate without it)
             os.environ["GPU_MAX_HW_QUEUES"] = "1"
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -1,6 +1,6 @@
 // Sandbox for the GEMM kernel: per-phase shader-clock breakdown (wave 0 of every workgroup) for one problem.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -ffp-contract=fast -fno-slp-vectorize -I include -DVPTR_GEMM_TIMING
-//         tools/gemm_probe.hip vptr_amd/csrc/api.hip -o gpurun_out/gemm_probe ;  gemm_probe M N K amode bmode split_k
+//         tools/gemm_probe.hip vptr_amd/csrc/api.hip vptr_amd/csrc/gemm_p16.hip -o gemm_probe.bin ;  ./gemm_probe.bin M N K amode bmode split_k
 #include "../vptr_amd/csrc/gemm.hip"
 #include <cstdio>
 #include <cstdlib>

@@ -276,7 +276,7 @@ struct KSeg {
   const float* Bk = (mb).B + ((s) == 0 ? (int64_t)0 : ((s) == 1 ? ksB1 : ksB2));
 
 template <int NFN, int NPASS, int AMODE, int BMODE>
-__global__ __launch_bounds__(GNT, 4) void vptr_gemm_kernel(const vptr_gemm_desc p, const int k_chunk, const int epi_rows) {
+__global__ __launch_bounds__(GNT, 4) void vptr_gemm_kernel(const vptr_gemm_desc p, const int k_chunk) {
   constexpr int BN = 16 * NFN;
   constexpr int NFW = (NFN + 1) / 2;     // column fragments per wave
   constexpr int BROWS = 2 * NFW * 16;    // LDS rows of the B image (>= BN; the surplus rows feed never-stored fragments)
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(GNT, 4) void vptr_gemm_kernel(const vptr_gemm_desc 
   // (176-wide tiles only: with 64 / 128-wide tiles -- the auto-encoder's convs, M up to 655 360 -- the LDS round trip and its
   // barriers cost more than the short rows gain: stage-1 step 32.8 -> 35.3 ms; and no atomic accumulation: float atomics
   // stay scalar, so the round trip buys nothing)
-  if (NFN == 11 && epi_rows && !use_atomic && epi_vec_ok(p) && p.d_row_w == 0) gemm_epilogue_rows_halves<NFN>(p, mb, acc, reinterpret_cast<float*>(sraw), m0, n0, wm, wn, lr, lq, tid, split == 0, use_atomic);
+  if (NFN == 11 && !use_atomic && epi_vec_ok(p) && p.d_row_w == 0) gemm_epilogue_rows_halves<NFN>(p, mb, acc, reinterpret_cast<float*>(sraw), m0, n0, wm, wn, lr, lq, tid, split == 0, use_atomic);
   else gemm_epilogue_serial<NFN>(p, mb, acc, m0, n0, wm, wn, lr, lq, split == 0, use_atomic);
   TS(5)
   TS_FLUSH
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(GNT, 4) void vptr_gemm_kernel(const vptr_gemm_desc 
 // j+1 is interleaved, unit by unit, between the MFMA groups of step j: one barrier per step, one workgroup per CU.
 template <int NFN, int NPASS, int AMODE, int BMODE>
 __device__ __forceinline__ void gemm_tile_p(const vptr_gemm_desc& p, const Member& mb, __bf16* smem, const int m0, const int n0, const int kbeg,
-                                            const int kend, const bool first_split, const bool use_atomic, const bool epi_rows = true) {
+                                            const int kend, const bool first_split, const bool use_atomic) {
   constexpr int BN = 16 * NFN;
   constexpr int NFW = (NFN + 1) / 2;
   constexpr int BROWS = 2 * NFW * 16;
@@ -413,11 +413,7 @@ __device__ __forceinline__ void gemm_tile_p(const vptr_gemm_desc& p, const Membe
   StA stA0, stA1;
   StB stB0, stB1;
   TS_DECL
-  // VPTR_EXP_NOLOAD / VPTR_EXP_NOCVT: elimination experiments of tools/gemm_probe.hip (results in DESIGN.md section 4)
   auto loadAB = [&](StA& sa, StB& sb, const int kt) {  // operands of K-step kt into a register set
-#ifdef VPTR_EXP_NOLOAD
-    if (kt > 2) return;
-#endif
     int k0;
     const int sg = ks.seg(kbeg, kt, k0);
     KSEG_PTRS(mb, sg, Ak, Bk)
@@ -459,15 +455,11 @@ __device__ __forceinline__ void gemm_tile_p(const vptr_gemm_desc& p, const Membe
         acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mi], bh, acc[mi][ni], 0, 0, 0);
       }
       // this group's share of the conversion work for the next step
-#ifndef VPTR_EXP_NOCVT
 #pragma unroll
       for (int u = (ni * UT) / NFW; u < ((ni + 1) * UT) / NFW; ++u) {
         if (u < UA) cvA.template store_unit<NPASS>(nA, nA + (NPL - 1) * A_EL, tid, u);
-#ifndef VPTR_EXP_NOCVT_B
         else cvB.template store_unit<NPASS>(nB, nB + (NPL - 1) * B_EL, tid, u - UA);
-#endif
       }
-#endif
     }
   };
 
@@ -498,7 +490,7 @@ __device__ __forceinline__ void gemm_tile_p(const vptr_gemm_desc& p, const Membe
       TS(2)
     }
   }
-  if (epi_rows && !use_atomic && epi_vec_ok(p) && p.d_row_w == 0) gemm_epilogue_rows<NFN>(p, mb, acc, reinterpret_cast<float*>(smem), m0, n0, wm, wn, lr, lq, tid, first_split, use_atomic);
+  if (!use_atomic && epi_vec_ok(p) && p.d_row_w == 0) gemm_epilogue_rows<NFN>(p, mb, acc, reinterpret_cast<float*>(smem), m0, n0, wm, wn, lr, lq, tid, first_split, use_atomic);
   else gemm_epilogue<NFN, 1>(p, mb, acc, m0, n0, wm, wn, lr, lq, first_split, use_atomic);
   if constexpr (AMODE == VPTR_A_KSTRIDED) {
     if (p.a_rowsum && n0 == 0) {  // workgroup-uniform: column tile 0 owns the row sums of its A panel
@@ -527,7 +519,7 @@ __device__ __forceinline__ void gemm_tile_p(const vptr_gemm_desc& p, const Membe
 }
 
 template <int NFN, int NPASS, int AMODE, int BMODE>
-__global__ __launch_bounds__(GNT, 2) void vptr_gemm_kernel_p(const vptr_gemm_desc p, const int k_chunk, const int epi_rows) {
+__global__ __launch_bounds__(GNT, 2) void vptr_gemm_kernel_p(const vptr_gemm_desc p, const int k_chunk) {
   extern __shared__ __attribute__((aligned(16))) __bf16 smem[];
   const int logical = xcd_logical_block();
   const int tiles_n = (p.N + 16 * NFN - 1) / (16 * NFN);
@@ -538,7 +530,7 @@ __global__ __launch_bounds__(GNT, 2) void vptr_gemm_kernel_p(const vptr_gemm_des
   const Member mb = member_of(p, batched ? grp : 0);
   const int kbeg = split * k_chunk;
   gemm_tile_p<NFN, NPASS, AMODE, BMODE>(p, mb, smem, (tile / tiles_n) * GBM, (tile % tiles_n) * 16 * NFN, kbeg, min(p.K, kbeg + k_chunk),
-                                        split == 0, p.atomic || (!batched && (int)gridDim.x > tiles), epi_rows != 0);
+                                        split == 0, p.atomic || (!batched && (int)gridDim.x > tiles));
 }
 
 // Grouped launch: `count` independent problems (same operand modes / precision / NFN class) in one grid, no split-K.
@@ -569,28 +561,11 @@ __global__ __launch_bounds__(GNT, 2) void vptr_gemm_grouped_kernel(const vptr_ge
 // workgroups per CU in the grid the single-image loop wins (N = 2112: 228 vs 179 TFLOP/s); with ~1 per CU the pipelined
 // one does (N = 528, K = 2112: 237 vs 186).  2 = choose by grid size (default); 0 / 1 force one (tools/gemm_probe.hip).
 static int g_gemm_variant = 2;
-// VPTR_GEMM_EPI_ROWS: bit 0 = row-major epilogue in the pipelined kernels, bit 1 = in the single-image kernel (default 3;
-// 0 = fragment-layout epilogues everywhere; tools/ab_epi.sh A/B runs)
-static int epi_rows_flag() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("VPTR_GEMM_EPI_ROWS");
-    v = e ? atoi(e) : 3;
-  }
-  return v;
-}
-static int v4_min_tiles() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("VPTR_GEMM_V4_MIN_TILES");
-    v = e ? atoi(e) : 384;
-  }
-  return v;
-}
+constexpr int kV4MinTiles = 384;   // grids below this take the pipelined loop (vptr_amd/ops/core.py mirrors it for bench.py's kernel names)
 
 template <int NFN, int NPASS, int AM, int BM>
 static int launch_one(const vptr_gemm_desc& d, dim3 grid, int k_chunk, hipStream_t st) {
-  const bool pipelined = g_gemm_variant == 1 || (g_gemm_variant == 2 && ((int)grid.x < v4_min_tiles() || d.a_rowsum != nullptr));
+  const bool pipelined = g_gemm_variant == 1 || (g_gemm_variant == 2 && ((int)grid.x < kV4MinTiles || d.a_rowsum != nullptr));
   if (pipelined) {
     constexpr int NFW = (NFN + 1) / 2, BROWS = 2 * NFW * 16, NPL = (NPASS == 3) ? 2 : 1;
     constexpr int LOOP_BYTES = 2 * NPL * (GBM + BROWS) * GLP * (int)sizeof(__bf16);
@@ -604,9 +579,9 @@ static int launch_one(const vptr_gemm_desc& d, dim3 grid, int k_chunk, hipStream
       }
       attr_set = true;
     }
-    vptr_gemm_kernel_p<NFN, NPASS, AM, BM><<<grid, GNT, LDS_BYTES, st>>>(d, k_chunk, epi_rows_flag() & 1);
+    vptr_gemm_kernel_p<NFN, NPASS, AM, BM><<<grid, GNT, LDS_BYTES, st>>>(d, k_chunk);
   } else {
-    vptr_gemm_kernel<NFN, NPASS, AM, BM><<<grid, GNT, 0, st>>>(d, k_chunk, epi_rows_flag() & 2);
+    vptr_gemm_kernel<NFN, NPASS, AM, BM><<<grid, GNT, 0, st>>>(d, k_chunk);
   }
   return 0;
 }
@@ -684,7 +659,7 @@ __global__ void split_planes_kernel(const float* __restrict__ x, __bf16* __restr
 
 // CONV = false: plain k-contiguous operands A[M][K/32][64], B[N][K/32][64] (K % 32 == 0), up to three batch members.
 template <bool CONV>
-__global__ __launch_bounds__(GNT, 4) void vptr_conv_planes_kernel(const vptr_gemm_desc p, const int epi_rows) {
+__global__ __launch_bounds__(GNT, 4) void vptr_conv_planes_kernel(const vptr_gemm_desc p) {
   constexpr int NFN = 11, BN = 176;
   extern __shared__ __attribute__((aligned(1024))) unsigned char pl_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -808,7 +783,7 @@ __global__ __launch_bounds__(GNT, 4) void vptr_conv_planes_kernel(const vptr_gem
       }
     }
   }
-  if ((epi_rows || p.D_planes) && !p.atomic && epi_vec_ok(p)) {
+  if (!p.atomic && epi_vec_ok(p)) {
     __syncthreads();  // the last stage is still being read by slower waves
     gemm_epilogue_rows_halves<NFN>(p, mb, acc, reinterpret_cast<float*>(pl_smem), m0, n0, wm, wn, lr, lq, tid, true, false);
   } else {
@@ -847,7 +822,7 @@ static int launch_conv_planes(const vptr_gemm_desc& d, hipStream_t st) {
     attr_set = true;
   }
   const int tiles = ((d.M + GBM - 1) / GBM) * ((d.N + 175) / 176) * (conv ? 1 : d.batch);
-  vptr_conv_planes_kernel<true><<<tiles, GNT, 2 * PL_STAGE, st>>>(d, epi_rows_flag() & 2);
+  vptr_conv_planes_kernel<true><<<tiles, GNT, 2 * PL_STAGE, st>>>(d);
   return 0;
 }
 

@@ -338,7 +338,7 @@ template <int NFN, int EPI>   // EPI: 0 every option, 1 lean (bias / alpha / res
                               //      3 lean + DropPath row scale + dropout (out-projections, linear2: `x + drop_path(dropout(proj(.)))`)
 __device__ __forceinline__ void gemm_epilogue_rows_halves_batched(const vptr_gemm_desc& p, const Member& mb, f32x4 (&acc)[2][(NFN + 1) / 2], float* sE,
                                                           const int m0, const int n0, const int wm, const int wn, const int lr, const int lq,
-                                                          const int tid, const bool first_split, const bool use_atomic_in, long long* tm = nullptr) {
+                                                          const int tid, const bool first_split, const bool use_atomic_in) {
   constexpr int NFW = (NFN + 1) / 2, BN = 16 * NFN, PITCH = BN + 4, C4 = BN / 4, HR = GBM / 2, NPIECE = HR * C4;
   constexpr bool LEAN = EPI != 0, GRAD = EPI == 2;   // EPI 4 (round 5): lean + activation + saved pre-activation (Dpre) + dropout -- linear1 of every MLP
   const bool has_res = !GRAD && mb.res && first_split;
@@ -365,9 +365,6 @@ __device__ __forceinline__ void gemm_epilogue_rows_halves_batched(const vptr_gem
     bs[ni] = (has_bias && ok) ? mb.bias[col] : 0.f;
     cs[ni] = (colscale && ok) ? colscale[col] : 1.f;
   }
-#ifdef VPTR_P16_TIMING
-  if (tm) { float z = 0.f; for (int ni = 0; ni < NFW; ++ni) z += bs[ni]; if (z == 12345.678f) sE[0] = z; tm[0] = wall_clock64(); }
-#endif
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     f32x4 res[NIT];
@@ -398,9 +395,6 @@ __device__ __forceinline__ void gemm_epilogue_rows_halves_batched(const vptr_gem
       }
     }
     __syncthreads();
-#ifdef VPTR_P16_TIMING
-    if (tm) tm[1 + 2 * h] = wall_clock64();
-#endif
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int piece = it * GNT + tid;
@@ -457,9 +451,6 @@ __device__ __forceinline__ void gemm_epilogue_rows_halves_batched(const vptr_gem
         unsafeAtomicAdd(p.frame_stats + VPTR_FRAME_STATS_STRIDE * fr + 1, q8);
       }
     }
-#ifdef VPTR_P16_TIMING
-    if (tm) tm[2 + 2 * h] = wall_clock64();
-#endif
     if (h == 0) __syncthreads();
   }
 }

@@ -15,7 +15,7 @@ from .core import (  # noqa: F401
 )
 from .wgrad import (  # noqa: F401
     _wgrad_q, defer_wgrad, take_wgrads, requeue_wgrads, discard_wgrads, _reduce_q, defer_partial_reduce, flush_partial_reduces,
-    _wgrad_hold, hold_wgrads, _wgrad_side, _flush_wgrads_side, join_wgrad_stream, _auto_flush_wgrads, _pin_pool, _pin_pool_small,
+    _wgrad_hold, hold_wgrads, _auto_flush_wgrads, _pin_pool, _pin_pool_small,
     _wgrad_tune, _graph_keepalive, _graph_reserve, _upload_stats, reserve_graph_staging, _to_device_async, _wgrad_tune_book, _wgrad_tune_decide, _TUNE_SAMPLES, wgrad_tune_open,
     wgrad_tune_settle, plan_wgrad_launches, _launch_wgrad_group, convt_weight_grads, flush_wgrads, _split_k_for,
 )

@@ -28,11 +28,9 @@ class _Config:
     defer_ln_param_grads = os.environ.get("VPTR_DEFER_LN", "1") != "0"
     # grouped token-major weight gradients: transposed-store orientation for dW whose row count leaves eighth-full tiles; 0 = A/B switch
     wgrad_flip = os.environ.get("VPTR_WGRAD_FLIP", "1") != "0"
-    # partly filled last row tiles as separate problems launched after all full tiles (equal-duration tiles stay in step); 0 = A/B switch
-    wgrad_split = os.environ.get("VPTR_WGRAD_SPLIT", "0") != "0"   # measured: no change (7.03 vs 7.05 ms bare launch): off
     wgrad_token_split = os.environ.get("VPTR_WGRAD_TOKEN_SPLIT", "1") != "0"   # small weight-gradient groups cut into token ranges (stock-DDP / autograd.grad paths)
-    # tile rows of the grouped weight-gradient launches: 128 (rounds 1 - 4), 256 (tall problems on 256 x 176 tiles, one workgroup per CU:
-    # 352 vs 300 TFLOP/s on the 2112- / 1584-row problems) or 192 (three stages); profiles/r05_wgrad_rows_ab.log
+    # tile rows of the grouped weight-gradient launches: 128 (rounds 1 - 4) or 256 (tall problems on 256 x 176 tiles, one workgroup per CU:
+    # 352 vs 300 TFLOP/s on the 2112- / 1584-row problems); profiles/r05_wgrad_rows_ab.log
     # "auto" (default): per problem set, whichever of 128 / 256 measured faster (see _launch_wgrad_group)
     wgrad_rows = (lambda v: v if v == "auto" else int(v))(os.environ.get("VPTR_WGRAD_ROWS", "auto"))
     # stride-2 3x3 transposed convolutions as four parity-class gathers (ops.SubpixelWeights) instead of one 9-tap gather form; 0 = A/B
@@ -41,9 +39,6 @@ class _Config:
     # P16 ("convert once") operands for every nn.Linear-shaped GEMM whose dimensions are multiples of 16 (precision 3 only):
     # the GEMMs stage pre-split bf16 hi / lo granules with global_load_lds instead of splitting fp32 in their main loops
     use_p16 = os.environ.get("VPTR_P16", "1") != "0"
-    # weight-gradient chunks on a side stream during backward (see _flush_wgrads_side); 0 = one grouped launch at the end
-    wgrad_async = os.environ.get("VPTR_WGRAD_ASYNC", "0") == "1"
-    wgrad_chunk_tiles = int(os.environ.get("VPTR_WGRAD_CHUNK", "600"))
     # the transformer MLP as one autograd node (ops.mlp) instead of two ops.linear nodes; 0 = A/B switch
     fused_mlp = os.environ.get("VPTR_FUSED_MLP", "1") != "0"
     # LayerNorm((F,H,W)) statistics accumulated by the epilogue of the producing GEMM / depthwise convolution; 0 = separate pass (A/B)
@@ -158,6 +153,9 @@ def _c(t):
 # ------------------------------------------------------------------------------------------------------------------
 # raw GEMM
 # ------------------------------------------------------------------------------------------------------------------
+GEMM_V4_MIN_TILES = 384   # csrc/gemm.hip kV4MinTiles: smaller grids of the register-staged GEMMs take the pipelined loop
+
+
 def gemm_raw(A, B, D, M, N, K, a_mode=0, b_mode=0, lda=None, ldb=None, bias=None, colscale=None, alpha=1.0, act=ACT_NONE,
              Dpre=None, rowscale=None, rs_div=1, rs_mod=1, dropout_p=0.0, site=0, residual=None, act_after=False,
              atomic=False, split_k=1, conv=None, precision=None, seed=None, a_rowsum=None, batch_extra=None, kseg_extra=None,
@@ -222,13 +220,12 @@ def gemm_raw(A, B, D, M, N, K, a_mode=0, b_mode=0, lda=None, ldb=None, bias=None
             tiles = ((M + 127) // 128) * ((N + 175) // 176) * max(d.batch, 1)
             cus = torch.cuda.get_device_properties(A.device).multi_processor_count
             lean4 = (not lean and not lean3 and act_grad_src is None and colscale is None and rowscale is None and residual is None and act != ACT_NONE
-                     and not act_after and not atomic and frame_stats is None and os.environ.get("VPTR_GEMM_NO_EPI4") is None)
-            key = key + ("p16", 2 if act_grad_src is not None else (4 if lean4 else (3 if lean3 else int(lean))),
-                         (3 if os.environ.get("VPTR_GEMM_LONE_STAGES") == "3" else 4) if tiles <= cus else 2)
-        elif a_mode != 3:     # register-staged kernels: pipelined loop below 384 workgroups (csrc/gemm.hip launch_one), else single-image
+                     and not act_after and not atomic and frame_stats is None)
+            key = key + ("p16", 2 if act_grad_src is not None else (4 if lean4 else (3 if lean3 else int(lean))), 4 if tiles <= cus else 2)
+        elif a_mode != 3:     # register-staged kernels: pipelined loop below GEMM_V4_MIN_TILES workgroups (csrc/gemm.hip launch_one), else single-image
             cols = 16 * gemm_nfn(N)
             wgs = ((M + 127) // 128) * ((N + cols - 1) // cols) * max(split_k, 1) * max(d.batch, 1)
-            key = key + ("staged", "p" if (wgs < int(os.environ.get("VPTR_GEMM_V4_MIN_TILES", "384")) or a_rowsum is not None) else "s")
+            key = key + ("staged", "p" if (wgs < GEMM_V4_MIN_TILES or a_rowsum is not None) else "s")
         prof.append((key, 2.0 * M * N * K * max(d.batch, d.ksegs, 1), e0, e1))
     return D
 

@@ -22,10 +22,6 @@ def defer_wgrad(g, x, dW, N, K, M, db=None, alpha=1.0, p16=False):
     """record dW[N,K] += g[M,N]^T . x[M,K] (dW, and db if given, must be views of a flat gradient slab); with db the bias
     gradient db[N] += column sums of g rides on the same launch (vptr_gemm_desc::a_rowsum).  p16: g and x are P16 tensors."""
     _wgrad_q.append((g, x, dW, N, K, M, config.gemm_precision, db, float(alpha), bool(p16)))
-    if config.wgrad_async and not _wgrad_hold[0]:
-        _wgrad_side["tiles"] += ((N + 127) // 128) * ((K + 175) // 176)
-        if _wgrad_side["tiles"] >= config.wgrad_chunk_tiles:
-            _flush_wgrads_side()
     # one end-of-backward callback per recorded call: flush_wgrads is idempotent, and registering every time stays correct
     # when an earlier backward died before its callbacks ran (a "callback already queued" flag would then be stale)
     try:
@@ -112,50 +108,9 @@ class hold_wgrads:
         return False
 
 
-# ---- weight gradients on a side stream, overlapped with the rest of the backward pass -------------------------------------------
-# The grouped weight-gradient launch is MFMA-bound, about half of the backward pass's other kernels are HBM-bound (normalisation,
-# attention cores, LayerNorm) or leave CUs idle (240-tile GEMMs): instead of one launch at the very end, the recorded problems are
-# flushed in chunks of >= config.wgrad_chunk_tiles tiles onto a second HIP stream while backward keeps running on the main one.
-# g and x stay alive through record_stream (the caching allocator defers their reuse until the side stream has passed them).
-_wgrad_side = {"stream": None, "tiles": 0, "dirty": False}
-
-
-def _flush_wgrads_side():
-    items = list(_wgrad_q)
-    del _wgrad_q[:]
-    _wgrad_side["tiles"] = 0
-    if not items:
-        return
-    cur = torch.cuda.current_stream()
-    if _wgrad_side["stream"] is None:
-        _wgrad_side["stream"] = torch.cuda.Stream()
-    side = _wgrad_side["stream"]
-    side.wait_stream(cur)          # every operand recorded so far has been produced on the main stream
-    with torch.cuda.stream(side):
-        # never the panel-synchronous persistent kernel here: it assumes all its workgroups resident and owns the device-wide barrier
-        # words (include/vptr_hip.h), and a side-stream launch runs beside the main stream's backward kernels
-        _launch_wgrad_group(items, allow_sync=False)
-    for it in items:
-        it[0].record_stream(side)
-        it[1].record_stream(side)
-    _wgrad_side["dirty"] = True
-
-
-def join_wgrad_stream():
-    """make the current stream wait for weight-gradient chunks still running on the side stream (before the optimizer reads them)"""
-    if _wgrad_side["dirty"]:
-        torch.cuda.current_stream().wait_stream(_wgrad_side["stream"])
-        _wgrad_side["dirty"] = False
-
-
 def _auto_flush_wgrads():
     if not _wgrad_hold[0]:
-        flush_partial_reduces()
-        if config.wgrad_async and _wgrad_q:
-            _flush_wgrads_side()
-        else:
-            flush_wgrads()
-        join_wgrad_stream()
+        flush_wgrads()
 
 
 _pin_pool = {"slots": [], "next": 0}
@@ -183,8 +138,6 @@ def _to_device_async(host_bytes, dev):
     n = len(host_bytes)
     _upload_stats["count"] += 1
     _upload_stats["max_bytes"] = max(_upload_stats["max_bytes"], n)
-    if os.environ.get("VPTR_SYNC_UPLOAD") == "1":
-        return torch.frombuffer(bytearray(host_bytes), dtype=torch.uint8).to(dev)
     if torch.cuda.is_current_stream_capturing():
         # the copy becomes a memcpy node that reads the HOST buffer at every replay: it gets a pinned buffer of its own that is
         # never reused (the rotating pool below is rewritten by later eager launches -- replays would upload stale descriptors)
@@ -257,37 +210,17 @@ def wgrad_tune_settle():
             _wgrad_tune_decide(t, final=True)
 
 
-def plan_wgrad_launches(probs, cols, p16, atomic, allow_sync, rows_mode, split_rem=False, token_split=True):
+def plan_wgrad_launches(probs, cols, p16, atomic, allow_sync, rows_mode, token_split=True):
     """Pure planning step of the grouped weight-gradient flush (no tensors, no launches: tests/test_cpu.py drives it with made-up
     addresses).  probs: (A ptr, B ptr, D ptr, rowsum ptr, lda, ldb, ldd, rows, cols, tokens, alpha, transposed) per weight, pointers as
     integers, leading dimensions in floats.  Returns [(sub-problems, vouch)]: one entry per kernel launch, every sub-problem the same
     tuple + its tile rows as a 13th element where they are not 128; `vouch` = every sub-problem of the launch walks the same number of
-    tokens (the panel-synchronous persistent kernel may serve it).  Rows of a problem are cut between a 256- (or 192-) row launch and
+    tokens (the panel-synchronous persistent kernel may serve it).  Rows of a problem are cut between a 256-row launch and
     the 128-row launch; a small group is cut into token ranges that accumulate into one destination; problems of different token
     counts go to different persistent launches."""
     subs = []
     for (ap, bp, dp, rp, lda, ldb, ldd, rows_, cols_, M, alpha, flip) in probs:
         small_group = p16 and atomic and token_split and len(probs) <= 3   # one layer's launch: token ranges on 128-row tiles (below)
-        if p16 and atomic and rows_mode == 192 and not small_group and rows_ >= 384:
-            # 192 x 176 tiles (three stages, one workgroup per CU): 2112 = 11 x 192 exactly, 528 = 2.75 (three tiles, the last 3/4 full,
-            # against 4.125 128-row tiles); a remainder that pads a 128-row tile less than a 192-row one joins the 128-row launch
-            rem = rows_ % 192
-            to128 = 0      # trailing rows handed to the 128-row launch
-            if flip and rp:   # the column sums of a flipped problem need a free 16-row fragment in the tile that holds its last rows
-                if rem == 0:
-                    to128 = 192
-                elif 192 - rem < 16:
-                    to128 = rem
-            elif rem and (192 - rem) > ((rem + 127) // 128) * 128 - rem:
-                to128 = rem
-            if to128:
-                full = rows_ - to128
-                subs.append((ap, bp, dp, 0 if flip else rp, lda, ldb, ldd, full, cols_, M, alpha, flip, 192))
-                subs.append((ap + full * 4, bp, dp + (full * 4 if flip else full * ldd * 4), (rp + (0 if flip else full * 4)) if rp else 0,
-                             lda, ldb, ldd, to128, cols_, M, alpha, flip, 128))
-            else:
-                subs.append((ap, bp, dp, rp, lda, ldb, ldd, rows_, cols_, M, alpha, flip, 192))
-            continue
         if p16 and atomic and rows_mode == 256 and not small_group and rows_ >= 1024 and (rows_ // 256) * 256 >= 0.85 * rows_:
             # tall problems on 256 x 176 tiles (1.47x the flops per staged byte, one workgroup per CU): the multiple-of-256 part
             # goes to the 256-row launch, the rest of the rows stays a 128-row problem (and keeps the bias gradient of a flipped one)
@@ -298,20 +231,8 @@ def plan_wgrad_launches(probs, cols, p16, atomic, allow_sync, rows_mode, split_r
                 subs.append((ap + full * 4, bp, dp + (full * 4 if flip else full * ldd * 4), (rp + (0 if flip else full * 4)) if rp else 0,
                              lda, ldb, ldd, rem256, cols_, M, alpha, flip, 128))
             continue
-        rem = rows_ % 128
-        if p16 and split_rem and rem and rows_ > 128:
-            # the partly filled last row tile of every problem becomes a problem of its own, launched after all full tiles: full
-            # tiles then all take the same time, so the tiles that share an operand panel stay in step (and in one L2), instead
-            # of being scattered by the short tiles that used to finish early between them
-            full = rows_ - rem
-            subs.append((ap, bp, dp, 0 if flip else rp, lda, ldb, ldd, full, cols_, M, alpha, flip))
-            subs.append((ap + full * 4, bp, dp + (full * 4 if flip else full * ldd * 4), (rp + (0 if flip else full * 4)) if rp else 0,
-                         lda, ldb, ldd, rem, cols_, M, alpha, flip))
-        else:
-            subs.append((ap, bp, dp, rp, lda, ldb, ldd, rows_, cols_, M, alpha, flip))
+        subs.append((ap, bp, dp, rp, lda, ldb, ldd, rows_, cols_, M, alpha, flip))
 
-    if p16 and split_rem:
-        subs.sort(key=lambda t: (0 if t[7] >= 128 else 1, -t[7] * t[8], t[1], t[2]))   # full-tile problems first (largest first), remainders last
     def trows(sub):
         return sub[12] if len(sub) > 12 else 128
 
@@ -409,7 +330,7 @@ def _launch_wgrad_group(its, atomic=1, allow_sync=True):
                 a, b, rows_, cols_, lda, ldb = g, x, N, K, g.stride(0), x.stride(0)
             ap, bp, dp, rp, ldd = a.data_ptr(), b.data_ptr(), dW.data_ptr(), (db.data_ptr() if db is not None else 0), dW.stride(0)
             probs.append((ap, bp, dp, rp, lda, ldb, ldd, rows_, cols_, M, alpha, flip))
-        launches = plan_wgrad_launches(probs, cols, p16, atomic, allow_sync, rows_mode, split_rem=config.wgrad_split,
+        launches = plan_wgrad_launches(probs, cols, p16, atomic, allow_sync, rows_mode,
                                        token_split=config.wgrad_token_split and not config.deterministic)
 
         def trows(sub):
@@ -443,8 +364,6 @@ def _launch_wgrad_group(its, atomic=1, allow_sync=True):
                 lflops += 2.0 * rows_ * cols_ * M
             if tr == 256:
                 descs[0].split_k = -2 if vouch else -3   # 256-row tiles: panel-synchronous / plain (include/vptr_hip.h)
-            elif tr == 192:
-                descs[0].split_k = -4 if vouch else -5   # 192-row tiles, three stages
             elif vouch:
                 descs[0].split_k = -1     # every problem walks the same number of tokens: the panel-synchronous launch may serve the group (VPTR_WGRAD_SYNC)
             raw = _to_device_async(bytes(descs), dev)
@@ -517,7 +436,7 @@ def flush_wgrads(chunks=1, on_chunk=None):
     del _wgrad_q[:]
     if chunks <= 1 or len(items) < 2 * chunks:
         # largest problems first (their 51-tile waves fill the chip; the 15-tile problems then pack the tail), problems that read the
-        # same X next to each other: 8.55 -> 8.42 ms on the K64 step's 196 problems (tools/wgrad_ab.sh)
+        # same X next to each other: 8.55 -> 8.42 ms on the K64 step's 196 problems (round-4 A/B)
         items.sort(key=lambda it: (-it[3] * it[4], it[1].data_ptr(), it[2].data_ptr()))
         _launch_wgrad_group(items)
         if on_chunk is not None:
@@ -538,9 +457,8 @@ def flush_wgrads(chunks=1, on_chunk=None):
         # largest problems first, problems that read the same X next to each other
         # plain launch for the chunks: the persistent panel-synchronous kernel assumes that ALL its 512 workgroups are resident at once (every
         # CU's whole LDS), and a chunk runs beside the all-reduce kernels of the previous one -- a displaced workgroup would cost the others
-        # a bounded-spin time-out (VPTR_WGRAD_SYNC_CHUNKS=1 allows it anyway)
-        _launch_wgrad_group(sorted(items[lo:hi], key=lambda it: (-it[3] * it[4], it[1].data_ptr(), it[2].data_ptr())),
-                            allow_sync=os.environ.get("VPTR_WGRAD_SYNC_CHUNKS") == "1")
+        # a bounded-spin time-out
+        _launch_wgrad_group(sorted(items[lo:hi], key=lambda it: (-it[3] * it[4], it[1].data_ptr(), it[2].data_ptr())), allow_sync=False)
         if on_chunk is not None:
             on_chunk(items[hi][2].data_ptr() if hi < len(items) else None)
         lo = hi
