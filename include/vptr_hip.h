@@ -43,6 +43,12 @@ int vptr_get_deterministic(void);
  * out_dev[8] (device ints) = per XCD, how many workgroups gave up a bounded wait since the library was loaded.  All zero = every
  * participant was resident whenever somebody waited for it. */
 int vptr_wgrad_sync_stats(int* out_dev, vptr_stream_t stream);
+/* Which kernel served the grouped weight-gradient launches (token-major P16 operands): out_host[0 .. n) (HOST ints, 1 <= n <= 5) = launches
+ * since the library was loaded of  0: plain 128-row tiles, atomic adds;  1: plain 128-row tiles, plain stores (atomic = 0);  2: persistent
+ * panel-synchronous 128-row tiles;  3: plain 256-row tiles;  4: persistent 256-row tiles.  Counted on the host when a launch is enqueued (a
+ * captured launch counts once, at capture); no device work, no synchronisation.  The persistent kernels fall back to the plain ones
+ * without an error (see vptr_gemm_grouped): this is how a caller tells which one ran. */
+int vptr_wgrad_kernel_counts(int* out_host, int n);
 /* Library-owned device state (the ONE exception to "no global mutable state"): the persistent panel-synchronous launch keeps its
  * per-XCD arrival counters in a module-scope __device__ array (512 ints, zero at load, left zero by every launch) and assumes that all
  * of its workgroups are resident.  Contract: AT MOST ONE such launch in flight per device, on one stream, with nothing else competing
@@ -158,7 +164,9 @@ typedef struct vptr_gemm_desc {
      (D is [N, ldd]), and a_rowsum then receives the column sums of the B operand: a_rowsum[n] += alpha * sum_t B[t][n].  The host
      uses it to put the 176-wide tile side on the dimension it divides: dW[528][2112] = dY^T . X is computed as X^T . dY (A = X,
      B = dY: 17 x 3 tiles instead of 5 x 12 with one eighth-full row tile in five) and lands in dW's own layout; the bias gradient
-     (column sums of dY) rides in a wave row of the last row tile that lies beyond M (needs >= 32 such rows: M % 128 in 1..96). */
+     (column sums of dY) rides in the first 16-row fragment of the last row tile that lies entirely beyond M: the kernel needs one such
+     fragment, i.e. M % TR in 1 .. TR - 16 (TR = tile rows, 128 or 256); the host asks for more (ops._launch_wgrad_group flips only when
+     128 - M % 128 >= 32).  A flipped problem with a_rowsum and NO free fragment loses its column sums without an error. */
   int d_transposed;
   /* fp32-staged kernels (a_mode 0 .. 2), fragment-layout epilogues only (no residual / Dpre): d_row_w > 0 sends output row m to row
      m + d_row_w * (m / d_row_w) + d_row_off of D (row pitch ldd).  With ldd = 2 * Cout, d_row_w = IW, d_row_off = py * IW and
@@ -254,6 +262,10 @@ int vptr_gemm_tile_cols(int N);
  *     -1   panel-synchronous persistent launch, 128 x 176 tiles (needs equal token counts and >= 1024 tiles; see the contract above)
  *     -2 / -3   256 x 176 tiles, one workgroup per CU (1.47x the flops per staged operand byte): persistent (>= 512 tiles) / plain
  *     < -3      rejected
+ *   atomic = 0 (token-range sub-problems whose destinations are written once): plain 128-row launch with plain stores, whatever split_k.
+ * The persistent launches fall back to the plain launch of the same tile rows WITHOUT an error when the group has fewer tiles than the
+ * threshold, when VPTR_WGRAD_SYNC=0 or the occupancy query (made once per process) says fewer than 2 workgroups fit per CU, or when the
+ * CU count is not a multiple of 4 (128 rows) / 8 (256 rows); vptr_wgrad_kernel_counts tells which kernel ran.
  * vptr_amd.ops.plan_wgrad_launches is the worked example of cutting a backward pass's problems into such launches. */
 int vptr_gemm_grouped(const vptr_gemm_desc* proto, const vptr_gemm_desc* descs_dev, const int* tile_start_dev, int count,
                       int total_tiles, vptr_stream_t stream);

@@ -140,6 +140,25 @@ def test_library_exports_every_declared_symbol():
     assert ctypes.sizeof(_lib.GemmDesc) % 8 == 0
 
 
+def test_wgrad_kernel_counts_query():
+    """vptr_wgrad_kernel_counts (which grouped weight-gradient kernel ran): host-side counters, all zero in a freshly loaded library (a
+    child process: in a GPU run of the whole suite this process has launched them); n outside 1 .. 5 and a null output are rejected"""
+    import subprocess
+    code = ("import ctypes\n"
+            "from vptr_amd import _lib\n"
+            "out = (ctypes.c_int * 5)(*([-1] * 5))\n"
+            "assert _lib.lib.vptr_wgrad_kernel_counts(out, 5) == 0\n"
+            "print(list(out))\n"
+            "one = (ctypes.c_int * 5)(*([-1] * 5))\n"
+            "assert _lib.lib.vptr_wgrad_kernel_counts(one, 1) == 0 and list(one) == [0, -1, -1, -1, -1]\n"
+            "for n in (0, 6, -1):\n"
+            "    assert _lib.lib.vptr_wgrad_kernel_counts(out, n) != 0 and b'1 .. 5' in _lib.lib.vptr_last_error(), n\n"
+            "assert _lib.lib.vptr_wgrad_kernel_counts(None, 5) != 0\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert r.stdout.strip().splitlines()[-1] == "[0, 0, 0, 0, 0]", r.stdout
+
+
 def test_graft_entry_build_runs():
     """the driver's build check (`__graft_entry__.build()`): compiles what changed, imports the package, checks the ABI version"""
     import importlib

@@ -19,6 +19,8 @@
 // study (nt 290-315 TFLOP/s, tn 230-265 TFLOP/s at the model's shapes vs 200-237 / 159 for the register-staged kernels).
 #include "gemm_shared.h"
 
+#include <atomic>
+
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 
@@ -347,10 +349,12 @@ __device__ __forceinline__ void wgrad_p16_tile(const vptr_gemm_desc& p, const in
   }
   // bias gradient: column tile 0 only, odd wave column, its 6th (otherwise idle) fragment multiplies by ones: acc[mi][5][r] =
   // sum_t G[t][row] for every column of the fragment
-  const bool flip = p.d_transposed != 0;   // D stored transposed; a_rowsum = column sums of B, taken by a wave row beyond M (see vptr_hip.h)
+  const bool flip = p.d_transposed != 0;   // D stored transposed; a_rowsum = column sums of B, taken by a fragment beyond M (see vptr_hip.h)
   const bool want_rowsum = !flip && p.a_rowsum != nullptr && n0 == 0 && wn == 1;   // wave-uniform
-  // column sums of B (flipped problems): the first 16-row FRAGMENT of the tile that lies entirely beyond M multiplies by ones instead
-  const int f0 = (NG - m0 + 15) >> 4;   // (the host admits a flipped problem with a bias only when at least 32 tile rows are free)
+  // column sums of B (flipped problems): the first 16-row FRAGMENT of the tile that lies entirely beyond M multiplies by ones instead.
+  // Needs one such fragment in the last row tile (M % TR in 1 .. TR - 16; with none the column sums are silently dropped); the host
+  // asks for more: it flips a problem only when 128 - M % 128 >= 32
+  const int f0 = (NG - m0 + 15) >> 4;
   const bool colsum_wave = flip && p.a_rowsum != nullptr && f0 < TR / 16 && wm == f0 / MI;   // wave-uniform
   const int cmi = f0 - wm * MI;          // that fragment's index among this wave's
   const __bf16 one = (__bf16)1.0f, zero = (__bf16)0.0f;
@@ -652,6 +656,16 @@ int vptr_gemm_p16_launch(vptr_gemm_desc& d, hipStream_t st) {
   return 0;
 }
 
+// launches of each grouped weight-gradient kernel since the library was loaded, counted when enqueued (a captured launch counts once, at
+// capture): 0 = plain 128-row (atomic), 1 = plain 128-row (stores), 2 = persistent 128-row, 3 = plain 256-row, 4 = persistent 256-row.
+// Host-side only, so that a test can tell which geometry served a launch -- the persistent ones fall back to plain ones without a message.
+static std::atomic<int> g_wgrad_launches[5];
+extern "C" int vptr_wgrad_kernel_counts(int* out_host, int n) {
+  VPTR_CHECK(out_host != nullptr && n >= 1 && n <= 5, "wgrad_kernel_counts: n must be 1 .. 5 (got %d)", n);
+  for (int i = 0; i < n; ++i) out_host[i] = g_wgrad_launches[i].load(std::memory_order_relaxed);
+  return 0;
+}
+
 int vptr_wgrad_p16_launch(const vptr_gemm_desc* proto, const vptr_gemm_desc* descs_dev, const int* tile_start_dev, int count, int total_tiles,
                           hipStream_t st) {
   VPTR_CHECK(proto->b_mode == VPTR_B_P16T && proto->precision == 3, "vptr_gemm_grouped(p16): both operands token-major P16, precision 3");
@@ -680,17 +694,24 @@ int vptr_wgrad_p16_launch(const vptr_gemm_desc* proto, const vptr_gemm_desc* des
   // 256-row tiles (split_k -2: panel-synchronous, -3: plain; the host counted this launch's tiles with 256 rows): one workgroup per CU
   if (proto->split_k == -2 || proto->split_k == -3) {
     VPTR_CHECK(proto->atomic, "vptr_gemm_grouped(p16): 256-row tiles accumulate with atomics only");
-    if (proto->split_k == -2 && sync && total_tiles >= 512 && cus > 0 && cus % 8 == 0)
+    if (proto->split_k == -2 && sync && total_tiles >= 512 && cus > 0 && cus % 8 == 0) {
       vptr_wgrad_p16_sync_kernel<16, 8, 4><<<cus, GNT, 2 * STG256, st>>>(descs_dev, tile_start_dev, count, total_tiles);
-    else
+      g_wgrad_launches[4].fetch_add(1, std::memory_order_relaxed);
+    } else {
       vptr_wgrad_p16_kernel<2, 0, 8, 4><<<total_tiles, GNT, 2 * STG256, st>>>(descs_dev, tile_start_dev, count);
+      g_wgrad_launches[3].fetch_add(1, std::memory_order_relaxed);
+    }
     return 0;
   }
-  if (sync && proto->split_k == -1 && proto->atomic && total_tiles >= 1024 && cus > 0 && cus % 4 == 0)   // two workgroups per CU (80 KB of LDS each)
+  if (sync && proto->split_k == -1 && proto->atomic && total_tiles >= 1024 && cus > 0 && cus % 4 == 0) {   // two workgroups per CU (80 KB of LDS each)
     vptr_wgrad_p16_sync_kernel<16><<<2 * cus, GNT, 2 * P16_STAGE, st>>>(descs_dev, tile_start_dev, count, total_tiles);
-  else if (!proto->atomic)
+    g_wgrad_launches[2].fetch_add(1, std::memory_order_relaxed);
+  } else if (!proto->atomic) {
     vptr_wgrad_p16_kernel<2, 1><<<total_tiles, GNT, 2 * P16_STAGE, st>>>(descs_dev, tile_start_dev, count);
-  else
+    g_wgrad_launches[1].fetch_add(1, std::memory_order_relaxed);
+  } else {
     vptr_wgrad_p16_kernel<2><<<total_tiles, GNT, 2 * P16_STAGE, st>>>(descs_dev, tile_start_dev, count);
+    g_wgrad_launches[0].fetch_add(1, std::memory_order_relaxed);
+  }
   return 0;
 }
