@@ -94,12 +94,23 @@ extern "C" int vptr_weight_planes(const vptr_wplane_entry* table_dev, const int*
 // K % 32 == 16: the last step's second granule does not exist; its DMA lanes re-fetch the first one (always valid memory)
 // and the A fragments of lanes lq >= 2 are zeroed.
 // ---------------------------------------------------------------------------------------------------------------------
-// LEAN: plain epilogue only (gemm_shared.h).  NST = 4: the instantiations for grids of at most one workgroup per CU (nothing else on
-// the CU hides a stall): four stages (the CU's whole 160 KB) with the DMA three K-steps ahead, its pieces issued between the MFMA groups
-// instead of in a burst after the barrier (cache-cold 10 240 x 528 x 2112: 79.7 -> 73.1 us in tools/gemm_p16_probe with three stages;
-// four stages: 77.9 -> 74.0 us inside the step).  NST = 2: two workgroups per CU.  Chosen by the launcher.
+// LEAN: plain epilogue only (gemm_shared.h).  NST = 2: two workgroups per CU, every wave stages and computes.  NST = 4: the instantiations
+// for grids of at most one workgroup per CU (nothing else on the CU hides a stall): four stages (the CU's whole 160 KB) with the DMA three
+// K-steps ahead, and 12 waves in two roles -- waves 0 .. 7 are the CONSUMERS (fragment reads and MFMAs only: the same fragment map and MFMA
+// order as NST = 2, so every output element is bit-for-bit the same), waves 8 .. 11 the LOADERS (10 of a K-step's 40 DMA pieces each, one
+// per SIMD beside two consumers).  The hand-off is the one barrier per K-step, over all 12 waves: before the barrier that opens step kt a
+// loader waits for its own pieces of step kt, after it it issues step kt + 3 into the stage everybody has just left.  The loaders leave
+// after the K loop (all their DMA has landed by then); the barriers of the epilogue count the live waves only.  Chosen by the launcher.
+constexpr int P16_NLOAD = 4;                                  // loader waves of the NST = 4 instantiations
+constexpr int P16_LONE_THREADS = GNT + 64 * P16_NLOAD;       // 768: three waves per SIMD, at most 168 VGPRs
+// s_waitcnt vmcnt(n) alone (gfx9 encoding: vmcnt[3:0] in bits 3:0, vmcnt[5:4] in bits 15:14; expcnt and lgkmcnt left at their maxima)
+constexpr int p16_vmcnt(const int n) { return 0x0f70 | (n & 15) | ((n >> 4) << 14); }
+// the loaders' DMA: the s_nop is the wait state between the write of M0 and the LDS-DMA that reads it
+#define P16_GLDS_NOP(laddr, gptr) \
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(laddr), "v"(gptr) : "memory")
+
 template <int EPI, int NST>   // EPI: 0 every epilogue option, 1 lean, 2 activation gradient, 3 lean + row scale + dropout, 4 activation + Dpre + dropout (gemm_shared.h)
-__global__ __launch_bounds__(GNT, NST >= 3 ? 2 : 4) void vptr_gemm_p16_kernel(const vptr_gemm_desc p) {
+__global__ __launch_bounds__(NST == 4 ? P16_LONE_THREADS : GNT, NST == 4 ? 3 : 4) void vptr_gemm_p16_kernel(const vptr_gemm_desc p) {
   static_assert(NST == 2 || NST == 4, "two stages (two workgroups per CU) or four (one)");
   constexpr int NFN = 11, BN = 176;
   extern __shared__ __attribute__((aligned(1024))) unsigned char p16_smem[];
@@ -123,6 +134,44 @@ __global__ __launch_bounds__(GNT, NST >= 3 ? 2 : 4) void vptr_gemm_p16_kernel(co
   const int64_t sA1 = nseg > 1 ? (p.A_x1 - p.A) * 4 : 0, sA2 = nseg > 2 ? (p.A_x2 - p.A) * 4 : 0;
   const int64_t sB1 = nseg > 1 ? (p.B_x1 - p.B) * 4 : 0, sB2 = nseg > 2 ? (p.B_x2 - p.B) * 4 : 0;
 
+  if (NST == 4 && __builtin_amdgcn_readfirstlane(wave) >= GNT / 64) {   // loader wave lw: pieces u = lw + 4 i of every K-step (u < 16: A rows 8u .., else B rows 8 (u - 16) ..)
+    const int lw = __builtin_amdgcn_readfirstlane(wave) - GNT / 64, pch = lane & 7, nkt = nk * nseg;
+    constexpr int NP = 40 / P16_NLOAD, NPA = 16 / P16_NLOAD;
+    const unsigned char* src[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const int u = lw + P16_NLOAD * i;
+      const int prow = (i < NPA ? u : u - 16) * 8 + (lane >> 3);
+      const int c = pch ^ ((prow >> 1) & 7);
+      src[i] = i < NPA ? Ab + (int64_t)min(m0 + prow, p.M - 1) * pa + c * 16 : Bb + (int64_t)min(n0 + prow, p.N - 1) * pb + c * 16;
+    }
+    // (prow >> 1) & 7 = ((lane >> 4) + 4 * lw) & 7 for every piece of this lane (u = lw + 4 i keeps the parity of lw)
+    const int tadj = (pch ^ (((lane >> 4) + 4 * lw) & 7)) >= 4 ? -64 : 0;
+    auto issue = [&](const int kt, const int stage) {
+      const int sg = (int)(kt >= nk) + (int)(kt >= 2 * nk);
+      const int kk = kt - sg * nk;
+      const int64_t off = (int64_t)kk * 128 + ((ktail && kk == nk - 1) ? tadj : 0);
+      int64_t oa = (sg == 0 ? (int64_t)0 : (sg == 1 ? sA1 : sA2)) + off, ob = (sg == 0 ? (int64_t)0 : (sg == 1 ? sB1 : sB2)) + off;
+      asm volatile("" : "+v"(oa), "+v"(ob));   // one 64-bit add per piece: hipcc otherwise re-associates the sums into three adds for each
+#pragma unroll
+      for (int i = 0; i < NP; ++i) P16_GLDS_NOP((uint32_t)(stage * P16_STAGE + (lw + P16_NLOAD * i) * 1024), src[i] + (i < NPA ? oa : ob));
+    };
+    issue(0, 0);
+    if (nkt > 1) issue(1, 1);
+    if (nkt > 2) issue(2, 2);
+    int sn = 3;   // the stage that step kt + 3 goes to
+    for (int kt = 0; kt < nkt; ++kt) {
+      // this wave's pieces of step kt have landed; steps kt + 1 and kt + 2 (NP pieces each) may still be in flight
+      if (kt + 2 < nkt) __builtin_amdgcn_s_waitcnt(p16_vmcnt(2 * NP));
+      else if (kt + 1 < nkt) __builtin_amdgcn_s_waitcnt(p16_vmcnt(NP));
+      else __builtin_amdgcn_s_waitcnt(p16_vmcnt(0));
+      __syncthreads();   // ... and everyone's; the consumers are done reading the stage of step kt - 1, which step kt + 3 overwrites
+      if (kt + 3 < nkt) issue(kt + 3, sn);
+      sn = (sn + 1) & 3;
+    }
+    return;   // nothing in flight: the last wait was vmcnt(0), nothing was issued after it
+  }
+
   const unsigned char* srcA[2];
   const unsigned char* srcB[3];
   int tadj;   // this lane's chunk is in the second granule of a K-step: -64 in a tail step (the same for all its pieces)
@@ -144,7 +193,6 @@ __global__ __launch_bounds__(GNT, NST >= 3 ? 2 : 4) void vptr_gemm_p16_kernel(co
     const int c = pch ^ (((lane >> 4) + 4 * wave) & 7);
     tadj = c >= 4 ? -64 : 0;
   }
-  constexpr int NPIECE = 5;
   auto issue1 = [&](const int kt, const int stage, const int i) {   // piece i of this wave: 0, 1 = A, 2 .. 4 = B
     const int sg = (int)(kt >= nk) + (int)(kt >= 2 * nk);
     const int kk = kt - sg * nk;
@@ -176,18 +224,12 @@ __global__ __launch_bounds__(GNT, NST >= 3 ? 2 : 4) void vptr_gemm_p16_kernel(co
   }
   // lo chunk = hi chunk + 2 under the XOR swizzle: (ch + 2) ^ f = (ch ^ f) ^ 2 because bit 1 of ch is clear
   const int nkt = nk * nseg;
-  issue(0, 0);
-  if (NST >= 3 && nkt > 1) issue(1, 1);
-  if (NST >= 4 && nkt > 2) issue(2, 2);
-  int sc = 0, sn = NST - 1;   // NST >= 3: stage of step kt, stage that step kt + NST - 1 goes to
+  if (NST == 2) issue(0, 0);
   for (int kt = 0; kt < nkt; ++kt) {
-    // step kt has landed: with three stages step kt + 1 (5 pieces per wave) may still be in flight
-    if (NST >= 4 && kt + 2 < nkt) __builtin_amdgcn_s_waitcnt(0x0f70 | (2 * NPIECE));   // four stages: steps kt + 1 and kt + 2 may be in flight
-    else if (NST >= 3 && kt + 1 < nkt) __builtin_amdgcn_s_waitcnt(0x0f70 | NPIECE);
-    else __builtin_amdgcn_s_waitcnt(0x0f70);
-    __syncthreads();                      // ... for every wave, and everyone is done reading the stage the next DMA overwrites
+    if (NST == 2) __builtin_amdgcn_s_waitcnt(0x0f70);   // this wave's pieces of step kt have landed (NST = 4: the loaders wait for theirs)
+    __syncthreads();                                    // ... and everyone's, and everyone is done reading the stage the next DMA overwrites
     if (NST == 2 && kt + 1 < nkt) issue(kt + 1, (kt + 1) & 1);
-    const unsigned char* st = p16_smem + (NST >= 3 ? sc : (kt & 1)) * P16_STAGE;
+    const unsigned char* st = p16_smem + (kt & (NST - 1)) * P16_STAGE;
     bf16x8 ah[2], al[2];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
@@ -216,7 +258,6 @@ __global__ __launch_bounds__(GNT, NST >= 3 ? 2 : 4) void vptr_gemm_p16_kernel(co
         bh[(ni + 1) & 1] = *reinterpret_cast<const bf16x8*>(st + offBh[ni + 1]);
         bl[(ni + 1) & 1] = *reinterpret_cast<const bf16x8*>(st + (offBh[ni + 1] ^ 32));
       }
-      if (NST >= 3 && ni < 5 && kt + NST - 1 < nkt) issue1(kt + NST - 1, sn, ni);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi) {
@@ -226,17 +267,13 @@ __global__ __launch_bounds__(GNT, NST >= 3 ? 2 : 4) void vptr_gemm_p16_kernel(co
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (NST >= 3) {
-      sc = sc == NST - 1 ? 0 : sc + 1;
-      sn = sn == NST - 1 ? 0 : sn + 1;
-    }
   }
   constexpr bool LEAN = EPI != 0;
   if (LEAN) {
     __syncthreads();  // the last stage is still being read by slower waves
     gemm_epilogue_rows_halves_batched<NFN, EPI>(p, mb, acc, reinterpret_cast<float*>(p16_smem), m0, n0, wm, wn, lr, lq, tid, true, false);
-  } else if (NST >= 3 && !p.atomic && epi_vec_ok(p)) {
-    // the full epilogue with its operand loads batched: affordable under this instantiation's 256-register budget
+  } else if (NST == 4 && !p.atomic && epi_vec_ok(p)) {
+    // the full epilogue with its operand loads batched: affordable under this instantiation's 168-register budget
     __syncthreads();
     gemm_epilogue_rows_halves_batched<NFN, 0>(p, mb, acc, reinterpret_cast<float*>(p16_smem), m0, n0, wm, wn, lr, lq, tid, true, false);
   } else if (!p.atomic && epi_vec_ok(p)) {
@@ -571,7 +608,7 @@ static bool p16_reserve_lds() {
 
 template <int EPI>
 static void p16_launch(const vptr_gemm_desc& d, const int tiles, const bool lone, hipStream_t st) {
-  if (lone) vptr_gemm_p16_kernel<EPI, 4><<<tiles, GNT, 4 * P16_STAGE, st>>>(d);
+  if (lone) vptr_gemm_p16_kernel<EPI, 4><<<tiles, P16_LONE_THREADS, 4 * P16_STAGE, st>>>(d);
   else vptr_gemm_p16_kernel<EPI, 2><<<tiles, GNT, 2 * P16_STAGE, st>>>(d);
 }
 
@@ -635,7 +672,8 @@ int vptr_gemm_p16_launch(vptr_gemm_desc& d, hipStream_t st) {
   const bool lean4 = !lean && !lean3 && !d.colscale && !d.rowscale && !d.residual && !d.act_after && !d.atomic &&
                      d.act != VPTR_ACT_NONE && !d.act_grad_src && !d.frame_stats && d.batch == 1 && !d.batch_accum &&
                      ((ebits | reinterpret_cast<uintptr_t>(d.Dpre)) & 15) == 0 && (d.N & 3) == 0 && (d.ldd & 3) == 0;
-  // at most one workgroup per CU: the four-stage instantiation (all 160 KB of LDS, the DMA three K-steps ahead); else two stages
+  // at most one workgroup per CU: the four-stage instantiation (all 160 KB of LDS, four loader waves keep the DMA three K-steps ahead of the
+  // eight computing ones); else two stages
   const bool lone = tiles <= vptr_cu_count();
   if (d.frame_stats)   // served by the lean epilogue only: no fallback
     VPTR_CHECK(d.frame_rows >= 64 && d.frame_rows % 64 == 0 && d.M % 64 == 0 && !d.act_grad_src && lean && d.batch == 1,
