@@ -159,3 +159,53 @@ def sampled_post_params_close(state_dicts, z, lr, rel_tol, max_flip_frac=0.03):
     assert relerr < rel_tol, relerr
     assert bad <= max_flip_frac * tot, (bad, tot, sorted(worst, reverse=True)[:12])
     return relerr
+
+
+# ---- fp64 reference builders of the stage-1 op tests (tests/test_09_stage1_ops_gpu.py) and the TSLMA core test; each one is checked against an
+# independent formulation on the CPU (tests/test_cpu.py) so that a wrong reference fails there, not on the GPU box
+def unfold_kkc(x, KH, KW, stride, pad, pad_mode="zero"):
+    """im2col of an NCHW tensor in the column order of vptr_im2col_nhwc: [(b, oy, ox), (ky, kx, c)].  F.unfold orders its columns (c, ky, kx);
+    the padding is applied first (zeros or F.pad's reflection), so the patches are plain strided windows of the padded image."""
+    import torch.nn.functional as F
+    B, C = x.shape[:2]
+    if pad:
+        x = F.pad(x, (pad,) * 4, mode="reflect") if pad_mode == "reflect" else F.pad(x, (pad,) * 4)
+    cols = F.unfold(x, (KH, KW), stride=stride)                              # [B, C * KH * KW, OH * OW]
+    L = cols.shape[-1]
+    return cols.reshape(B, C, KH, KW, L).permute(0, 4, 2, 3, 1).reshape(B * L, KH * KW * C)
+
+
+def ts_rows(N, T, H, W, ws):
+    """token rows of every (window, sequence element) of the temporal-spatial window attention: [N * (H/ws) * (W/ws), T * ws * ws] int64 with
+    window b = (n, qh, qw), element s = (t, ph, pw) -> row ((n * T + t) * H + qh * ws + ph) * W + qw * ws + pw (H, W multiples of ws)"""
+    n, qh, qw, t, ph, pw = torch.meshgrid(torch.arange(N), torch.arange(H // ws), torch.arange(W // ws), torch.arange(T), torch.arange(ws),
+                                          torch.arange(ws), indexing="ij")
+    rows = ((n * T + t) * H + qh * ws + ph) * W + qw * ws + pw
+    return rows.reshape(N * (H // ws) * (W // ws), T * ws * ws)
+
+
+def ts_gather(x, N, T, H, W, ws):
+    """tokens [(n, t, h, w), C] -> [windows, T * ws * ws, C] (explicit gather by window)"""
+    rows = ts_rows(N, T, H, W, ws)
+    return x[rows.reshape(-1)].reshape(rows.shape[0], rows.shape[1], x.shape[-1])
+
+
+def ts_scatter(xw, N, T, H, W, ws):
+    """inverse of ts_gather: every token belongs to exactly one (window, element), so the scatter is a gather by the inverse permutation"""
+    rows = ts_rows(N, T, H, W, ws).reshape(-1)
+    inv = torch.empty_like(rows)
+    inv[rows] = torch.arange(rows.numel())
+    return xw.reshape(rows.numel(), xw.shape[-1])[inv]
+
+
+def reflect_fold_ref(dxpad, pad):
+    """adjoint of F.pad(mode="reflect"): dxpad [B, C, H + 2p, W + 2p] -> [B, C, H, W]; padded index q belongs to source |q - p| mirrored at
+    n - 1, and every padded row / column is ADDED onto the source row / column it mirrors (one axis after the other)"""
+    def fold(t, dim):
+        n = t.shape[dim] - 2 * pad
+        src = (torch.arange(n + 2 * pad) - pad).abs()
+        src = torch.where(src > n - 1, 2 * (n - 1) - src, src)
+        shape = list(t.shape)
+        shape[dim] = n
+        return torch.zeros(shape, dtype=t.dtype).index_add_(dim, src, t)
+    return fold(fold(dxpad, 2), 3)

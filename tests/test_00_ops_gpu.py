@@ -421,6 +421,106 @@ def test_attention_partial_head_groups(ops, dev, nh, C):
         assert rel(a.grad, c.grad) < 1e-4
 
 
+# (N, Tq, Tk, H, W, ws, C, nh): the K64 model's own geometry (head dim 66: 115 KB of dynamic LDS in the backward, 7 key groups that leave 50 of
+# the 512 threads without dK / dV ownership, 23 of the 24 accumulators, clamped duplicate keys in the last group); a cross case with Tq != Tk on
+# a non-square map with 2 x 3 windows per frame (head dim 6); Lq = 20 (not a multiple of the 16-query chunk); Lq = 12 < 16 at head dim 16;
+# 6 heads of 8; Lk = 168 = TS_NACC * (512 / 66), the backward's key limit
+TS_GEOMS = [(1, 10, 10, 8, 8, 4, 528, 8), (2, 3, 7, 4, 6, 2, 48, 8), (1, 5, 5, 4, 4, 2, 48, 8), (1, 3, 4, 6, 4, 2, 128, 8), (2, 2, 3, 4, 8, 4, 48, 6),
+            (1, 2, 42, 2, 2, 2, 528, 8)]
+
+
+def _ts_reference(q, k, v, go, N, Tq, Tk, H, W, ws, nh, mask=None):
+    """fp64 temporal-spatial window attention from an explicit gather by window (helpers.ts_gather) + O._heads + O._attend; returns o and the
+    gradients of (q, k, v) under the upstream gradient go"""
+    from helpers import ts_gather, ts_scatter
+    ins = [t.double().clone().requires_grad_(True) for t in (q, k, v)]
+    qw, kw, vw = ts_gather(ins[0], N, Tq, H, W, ws), ts_gather(ins[1], N, Tk, H, W, ws), ts_gather(ins[2], N, Tk, H, W, ws)
+    if mask is None:
+        o = O._attend(O._heads(qw, nh), O._heads(kw, nh), O._heads(vw, nh))
+    else:
+        with O.dropout_masks({"ts.probs": mask.double()}):
+            o = O._attend(O._heads(qw, nh), O._heads(kw, nh), O._heads(vw, nh), drop_site="ts.probs")
+    o = ts_scatter(o, N, Tq, H, W, ws)
+    (o * go.double()).sum().backward()
+    return o.detach(), [t.grad for t in ins]
+
+
+@pytest.mark.parametrize("N,Tq,Tk,H,W,ws,C,nh", TS_GEOMS)
+def test_temporal_spatial_window_attention(ops, dev, N, Tq, Tk, H, W, ws, C, nh):
+    """vptr_tsattn_fwd / vptr_tsattn_bwd (the TSLMA core, attn.hip) vs fp64: forward 5e-5, dq / dk / dv 1e-4 (the bars of the fp32 vector family)"""
+    q, k, v = rn((N * Tq * H * W, C), 80, 0.5), rn((N * Tk * H * W, C), 81, 0.5), rn((N * Tk * H * W, C), 82)
+    go = rn((N * Tq * H * W, C), 83)
+    o, grads = _ts_reference(q, k, v, go, N, Tq, Tk, H, W, ws, nh)
+    ds = [t.to(dev).requires_grad_(True) for t in (q, k, v)]
+    od = ops.temporal_spatial_window_attention(ds[0], ds[1], ds[2], N, Tq, Tk, H, W, ws, nh)
+    (od * go.to(dev)).sum().backward()
+    assert rel(od, o) < TOLA
+    for a, c in zip(ds, grads):
+        assert rel(a.grad, c) < 1e-4
+
+
+@pytest.mark.parametrize("N,Tq,Tk,H,W,ws,C,nh", TS_GEOMS[:2])
+def test_temporal_spatial_window_attention_dropout(ops, dev, N, Tq, Tk, H, W, ws, C, nh):
+    """the same with dropout 0.1 on the attention probabilities: the mask of element ((b * nh + h) * Lq + i) * Lk + j is regenerated through
+    vptr_dropout as (windows, nh, Lq, Lk) and injected into the reference (as tests/test_03 does for the other sites) -- same bars, forward and
+    backward; without the mask the reference must be far away"""
+    from vptr_amd._lib import check, lib, ptr, stream
+    p, site = 0.1, 7
+    Lq, Lk, windows = Tq * ws * ws, Tk * ws * ws, N * (H // ws) * (W // ws)
+    q, k, v = rn((N * Tq * H * W, C), 84, 0.5), rn((N * Tk * H * W, C), 85, 0.5), rn((N * Tk * H * W, C), 86)
+    go = rn((N * Tq * H * W, C), 87)
+    ops.manual_seed(dev, 2468)
+    ops.new_seed_scope(dev)
+    ds = [t.to(dev).requires_grad_(True) for t in (q, k, v)]
+    od = ops.temporal_spatial_window_attention(ds[0], ds[1], ds[2], N, Tq, Tk, H, W, ws, nh, dropout_p=p, site=site)
+    seed = ops.seed_tensor(dev).clone()
+    (od * go.to(dev)).sum().backward()
+    n = windows * nh * Lq * Lk
+    ones, md = torch.ones(n, device=dev), torch.empty(n, device=dev)
+    check(lib.vptr_dropout(ptr(ones), ptr(md), n, p, ptr(seed), site, stream()), "vptr_dropout")
+    mask = md.reshape(windows, nh, Lq, Lk).cpu()
+    assert 0.08 < float((mask == 0).float().mean()) < 0.12
+    o, grads = _ts_reference(q, k, v, go, N, Tq, Tk, H, W, ws, nh, mask)
+    assert rel(od, o) < TOLA
+    for a, c in zip(ds, grads):
+        assert rel(a.grad, c) < 1e-4
+    o_nomask, _ = _ts_reference(q, k, v, go, N, Tq, Tk, H, W, ws, nh)
+    assert rel(o_nomask, o) > 10 * TOLA          # the check would be vacuous otherwise
+
+
+def test_temporal_spatial_window_attention_key_limit(ops, dev):
+    """one key more than the backward's register accumulators hold (Tk * ws^2 = 172 > 24 * (512 / 66) = 168): an argument error from the host-side
+    check, before any launch"""
+    from vptr_amd._lib import check, lib, ptr, stream
+    N, Tq, Tk, H, W, ws, C, nh = 1, 2, 43, 2, 2, 2, 528, 8
+    q, k = torch.zeros((N * Tq * H * W, C), device=dev), torch.zeros((N * Tk * H * W, C), device=dev)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(k)
+    with pytest.raises(RuntimeError, match="exceeds 168 keys per window"):
+        check(lib.vptr_tsattn_bwd(ptr(q), ptr(k), ptr(k), ptr(q), ptr(dq), ptr(dk), ptr(dv), N, Tq, Tk, H, W, ws, C, nh, 0.0, None, 0, 0, stream()),
+              "vptr_tsattn_bwd")
+
+
+def test_tslma_forward_tokens_padded_map(ops, dev):
+    """TemporalSpatialLocalMultiheadAttention.forward_tokens on a map that needs PadBlock padding (H = 6, W = 5, ws = 4) vs the oracle's tslma:
+    the pad_tokens / crop_tokens wiring around the core, forward and both input gradients"""
+    import vptr_amd.model.vidhrformer as V
+    N, T1, T2, H, W, ws, C, nh = 2, 3, 2, 6, 5, 4, 48, 8
+    m = V.TemporalSpatialLocalMultiheadAttention(C, nh, ws, 0.0)
+    fill.apply_fill(m, 90)
+    P = {"t." + k_: v_.detach().double() for k_, v_ in m.state_dict().items()}
+    m = m.to(dev).eval().requires_grad_(False)
+    mem, query, res = rn((N, T1, H, W, C), 91), rn((N, T2, H, W, C), 92), rn((N, T2, H, W, C), 93)
+    Tlw, go = rn((T1 + T2, ws, ws, C), 94, 0.5), rn((N * T2 * H * W, C), 95)
+    mr, qr = mem.double().requires_grad_(True), query.double().requires_grad_(True)
+    ref = (res.double() + O.tslma(P, "t.", mr, qr, Tlw.double(), ws, nh)).reshape(-1, C)
+    (ref * go.double()).sum().backward()
+    md, qd = mem.reshape(-1, C).to(dev).requires_grad_(True), query.reshape(-1, C).to(dev).requires_grad_(True)
+    out = m.forward_tokens(md, qd, res.reshape(-1, C).to(dev), V.Geom(N, T2, H, W), T1, Tlw.to(dev), 0)
+    (out * go.to(dev)).sum().backward()
+    assert rel(out, ref) < TOLA
+    assert rel(md.grad, mr.grad.reshape(-1, C)) < 1e-4 and rel(qd.grad, qr.grad.reshape(-1, C)) < 1e-4
+
+
 def _proj_ref(ops, xq, xk, xv, Ws, bs, nh, attend):
     """composition of the separate nodes: three linears (alpha on q) + the attention core"""
     C = Ws[0].shape[0]
@@ -606,7 +706,9 @@ def test_conv7_ends(ops, dev, cimg, geom):
 
 
 def test_bnrelu_bwd_fused(dev):
-    """dx and the affine gradients of eval-BatchNorm + ReLU in one pass == the two separate kernels == autograd"""
+    """dx and the affine gradients of eval-BatchNorm + ReLU in one pass (vptr_bnrelu_bwd_fused) == autograd, and == the two separate kernels
+    (vptr_bnrelu_bwd, vptr_bnrelu_bwd_params) launched on the same inputs: dx bit for bit (one multiply per element in both), the column sums
+    within the fp32 vector bar (other summation order)"""
     from vptr_amd._lib import check, lib, ptr, stream
     for rows, C in ((3000, 64), (1111, 128), (517, 256), (300, 24)):
         xh = rn((rows, C), 120)
@@ -621,6 +723,12 @@ def test_bnrelu_bwd_fused(dev):
         check(lib.vptr_bnrelu_bwd_fused(ptr(dyd), ptr(yd), ptr(sg), ptr(wg), ptr(bg), ptr(dx), ptr(dw), ptr(db), rows, C, stream()), "fused")
         assert rel(dx, (y.detach() > 0).double() * dy.double() * sc.double()) < 1e-6
         assert rel(dw, wd_.grad) < 2e-5 and rel(db, bd.grad) < 2e-5
+        dx2, dw2, db2 = torch.empty((rows, C), device=dev), torch.zeros(C, device=dev), torch.zeros(C, device=dev)
+        check(lib.vptr_bnrelu_bwd(ptr(dyd), ptr(yd), ptr(sg), ptr(dx2), rows, C, stream()), "bnrelu_bwd")
+        check(lib.vptr_bnrelu_bwd_params(ptr(dyd), ptr(yd), ptr(wg), ptr(bg), ptr(dw2), ptr(db2), rows, C, stream()), "bnrelu_bwd_params")
+        assert torch.equal(dx2, dx)
+        assert rel(dw2, wd_.grad) < 2e-5 and rel(db2, bd.grad) < 2e-5
+        assert rel(dw2, dw.double().cpu()) < 2e-5 and rel(db2, db.double().cpu()) < 2e-5
 
 
 # ------------------------------------------------------------------------------------------------------------ optimizer

@@ -668,3 +668,58 @@ def test_winograd_filter_transform_matches_direct_convolution():
     Y = torch.einsum("ai,ijk,bj->kab", AT, M, AT)             # [Cout, 4, 4]
     ref = torch.nn.functional.conv2d(d, g)[0]
     assert float((Y - ref).abs().max()) < 1e-12
+
+
+# ---- the fp64 reference builders of the stage-1 / TSLMA op tests, each against an independent formulation ----------------------------------
+@pytest.mark.parametrize("K,stride,pad,pad_mode", [(3, 1, 1, "zero"), (3, 2, 1, "zero"), (4, 2, 1, "zero"), (4, 1, 1, "zero"), (3, 1, 1, "reflect"),
+                                                   (7, 1, 3, "reflect")])
+def test_unfold_kkc_is_the_conv_patch_matrix(K, stride, pad, pad_mode):
+    """helpers.unfold_kkc: patches [(b, oy, ox), (ky, kx, c)] @ weight[(co), (ky, kx, ci)]^T == F.conv2d on a non-square map (a swapped ky / kx
+    or a channel-major column order would not)"""
+    import torch.nn.functional as F
+    from helpers import unfold_kkc
+    B, C, Co, H, W = 2, 3, 5, 9, 7
+    x, w = fill.rand_normal((B, C, H, W), 1).double(), fill.rand_normal((Co, C, K, K), 2).double()
+    xp = F.pad(x, (pad,) * 4, mode="reflect") if pad_mode == "reflect" else F.pad(x, (pad,) * 4)
+    ref = F.conv2d(xp, w, stride=stride)
+    P = unfold_kkc(x, K, K, stride, pad, pad_mode)
+    assert P.shape == (B * ref.shape[2] * ref.shape[3], K * K * C)
+    out = (P @ w.permute(0, 2, 3, 1).reshape(Co, -1).t()).reshape(B, ref.shape[2], ref.shape[3], Co).permute(0, 3, 1, 2)
+    assert rel(out, ref) < 1e-14
+
+
+def test_ts_gather_matches_oracle_tslma():
+    """helpers.ts_gather / ts_scatter (explicit index gather by window) + O._heads + O._attend == the inner nn.MultiheadAttention of O.tslma
+    (which goes through O._ts_permute's pad / reshape / permute) on a tiny non-square case with several windows per frame and Tq != Tk"""
+    import torch.nn.functional as F
+    from helpers import ts_gather, ts_rows, ts_scatter
+    N, T1, T2, H, W, ws, C, nh = 2, 3, 2, 4, 6, 2, 12, 3
+    P = {"a.attn.in_proj_weight": fill.rand_normal((3 * C, C), 3, C ** -0.5).double(), "a.attn.in_proj_bias": fill.rand_normal((3 * C,), 4).double(),
+         "a.attn.out_proj.weight": fill.rand_normal((C, C), 5, C ** -0.5).double(), "a.attn.out_proj.bias": fill.rand_normal((C,), 6).double()}
+    mem, query = fill.rand_normal((N, T1, H, W, C), 7).double(), fill.rand_normal((N, T2, H, W, C), 8).double()
+    Tlw = fill.rand_normal((T1 + T2, ws, ws, C), 9).double()
+    ref = O.tslma(P, "a.", mem, query, Tlw, ws, nh)
+    rows = ts_rows(N, T2, H, W, ws)
+    assert sorted(rows.reshape(-1).tolist()) == list(range(N * T2 * H * W))            # a permutation of all tokens
+    Wq, Wk, Wv = P["a.attn.in_proj_weight"].chunk(3)
+    bq, bk, bv = P["a.attn.in_proj_bias"].chunk(3)
+    qw = ts_gather(query.reshape(-1, C), N, T2, H, W, ws) + Tlw[T1:].reshape(1, -1, C)
+    mw = ts_gather(mem.reshape(-1, C), N, T1, H, W, ws)
+    q = F.linear(qw, Wq, bq) * (C // nh) ** -0.5
+    k, v = F.linear(mw + Tlw[:T1].reshape(1, -1, C), Wk, bk), F.linear(mw, Wv, bv)
+    o = O._attend(O._heads(q, nh), O._heads(k, nh), O._heads(v, nh))
+    o = F.linear(ts_scatter(o, N, T2, H, W, ws), P["a.attn.out_proj.weight"], P["a.attn.out_proj.bias"])
+    assert rel(o, ref.reshape(-1, C)) < 1e-13
+    x = fill.rand_normal((N * T2 * H * W, C), 10)
+    assert torch.equal(ts_scatter(ts_gather(x, N, T2, H, W, ws), N, T2, H, W, ws), x)
+
+
+@pytest.mark.parametrize("H,W,pad", [(5, 7, 1), (2, 3, 1), (4, 6, 3), (8, 5, 3), (6, 6, 2)])
+def test_reflect_fold_ref_is_the_adjoint_of_reflection_padding(H, W, pad):
+    """helpers.reflect_fold_ref == torch.autograd.grad of F.pad(mode="reflect"), down to H = pad + 1 (a border pixel with three pre-images)"""
+    import torch.nn.functional as F
+    from helpers import reflect_fold_ref
+    x = fill.rand_normal((2, 3, H, W), 11).double().requires_grad_(True)
+    g = fill.rand_normal((2, 3, H + 2 * pad, W + 2 * pad), 12).double()
+    (ref,) = torch.autograd.grad(F.pad(x, (pad,) * 4, mode="reflect"), x, g)
+    assert rel(reflect_fold_ref(g, pad), ref) < 1e-15
