@@ -350,6 +350,16 @@ int vptr_tattn_bwd(const float* q, const float* k, const float* v, const float* 
                    int Nb, int Tq, int Tk, int HW, int C, int nh, int causal, float dropout_p, const uint64_t* seed_dev,
                    uint32_t site, float dq_scale /* as in vptr_winattn_bwd */, int p16, vptr_stream_t stream);
 
+/* One decoding step of the CAUSAL temporal attention against a key / value cache (eval only: no mask, no dropout).
+ * q, o: [rows, C], rows = N*H*W, one query per (sample, pixel), q pre-scaled by head_dim^-0.5.
+ * kcache, vcache: [Tcap][rows][C] fp32, TIME-MAJOR: slot j is one contiguous [rows, C] slab (so a step's key / value
+ * projections are written straight into slot t as a plain GEMM output).  Only slots 0 .. Tk-1 are read; the newest slot
+ * Tk-1 is the query's own frame, i.e. o[r, h] = softmax_j(q[r,h] . k[j,r,h]) v[j,r,h] over j < Tk is the last row of the
+ * causal attention over Tk frames.  p16 != 0: o is written as a P16 tensor (C % 16 == 0).
+ * Rejected without a launch: Tk < 1, Tk > Tcap, Tk > 64, C % nh != 0, p16 with C % 16 != 0, non-positive sizes. */
+int vptr_tattn_step(const float* q, const float* kcache, const float* vcache, float* o, int rows, int Tk, int Tcap, int C,
+                    int nh, int p16, vptr_stream_t stream);
+
 /* Temporal-spatial window attention (TemporalSpatialLocalMultiheadAttention, VidHRFormer_modules.py:219-284 with the
  * permutes of :444-484 folded into index arithmetic): q [(n,tq,h,w), C] (pre-scaled), k, v [(n,tk,h,w), C]; for every
  * ws x ws window and head the Tq*ws*ws queries attend to the Tk*ws*ws memory tokens of the same window.

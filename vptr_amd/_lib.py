@@ -84,6 +84,7 @@ SIGNATURES = {
     "vptr_winattn_bwd_workspace": [I],
     "vptr_tattn_fwd": [P, P, P, P, I, I, I, I, I, I, I, F, P, U, I, P],
     "vptr_tattn_bwd": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P, U, F, I, P],
+    "vptr_tattn_step": [P, P, P, P, I, I, I, I, I, I, P],
     "vptr_tsattn_fwd": [P, P, P, P, I, I, I, I, I, I, I, I, F, P, U, I, P],
     "vptr_tsattn_bwd": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, P, U, I, P],
     "vptr_colstats": [P, P, P, P, F, P, I, I, P],

@@ -799,6 +799,89 @@ extern "C" int vptr_tattn_fwd(const float* q, const float* k, const float* v, fl
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// one decoding step of the causal temporal attention against a time-major key / value cache [Tcap][rows][C]: one wave per
+// (row, head), no mask (the newest slot is the query's own frame), no LDS.  The kernel is a stream of the cache: lane l owns
+// V floats of the head, a key's head row is one contiguous load of the wave, the score is a wave sum, lane j keeps the score of
+// key j (Tk <= 64 = one key per lane) and the probabilities come back by lane broadcast for the value sum.
+// ------------------------------------------------------------------------------------------------------------
+template <int V> struct StepVec;
+template <> struct StepVec<1> {
+  float x;
+  __device__ __forceinline__ static StepVec ld(const float* p) { return {*p}; }
+  __device__ __forceinline__ float dot(const StepVec& b) const { return x * b.x; }
+  __device__ __forceinline__ void axpy(float a, const StepVec& b) { x += a * b.x; }
+  __device__ __forceinline__ void st(float* o, int64_t e, int p16) const { store1(o, e, x, p16); }
+};
+template <> struct StepVec<2> {
+  float x, y;
+  __device__ __forceinline__ static StepVec ld(const float* p) {
+    const float2 t = *reinterpret_cast<const float2*>(p);
+    return {t.x, t.y};
+  }
+  __device__ __forceinline__ float dot(const StepVec& b) const { return x * b.x + y * b.y; }
+  __device__ __forceinline__ void axpy(float a, const StepVec& b) { x += a * b.x; y += a * b.y; }
+  __device__ __forceinline__ void st(float* o, int64_t e, int p16) const {   // the pair half of store4: e is even
+    if (p16) vptr_p16_store2(reinterpret_cast<unsigned char*>(o), e, x, y);
+    else *reinterpret_cast<float2*>(o + e) = make_float2(x, y);
+  }
+};
+
+template <int V>  // V floats per lane and load: 2 when the head width is even (every head row is then 8-byte aligned), else 1
+__global__ __launch_bounds__(64) void tattn_step_kernel(const float* __restrict__ q, const float* __restrict__ kc,
+                                                        const float* __restrict__ vc, float* __restrict__ o, int rows, int Tk,
+                                                        int C, int nh, int p16) {
+  using Vec = StepVec<V>;
+  // workgroup b runs on XCD b % 8: the nh heads of a row (which share its cache lines) get the same XCD
+  const int h = (blockIdx.x >> 3) % nh, r = (blockIdx.x / (8 * nh)) * 8 + (blockIdx.x & 7), lane = threadIdx.x;
+  if (r >= rows) return;   // tail: the grid is rounded up to a multiple of 8 rows
+  const int hd = C / nh, n = hd / V, nch = (n + 63) >> 6;
+  const int64_t slab = (int64_t)rows * C, base = (int64_t)r * C + h * hd;
+  const bool in0 = lane < n;
+  const int e0 = min(lane, n - 1) * V;   // lanes past the head re-read its last element and contribute nothing
+  const Vec q0 = Vec::ld(q + base + e0);
+  float s = -INFINITY;
+#pragma unroll 4
+  for (int j = 0; j < Tk; ++j) {
+    const float* kr = kc + j * slab + base;
+    float part = in0 ? q0.dot(Vec::ld(kr + e0)) : 0.f;
+    for (int c = 1; c < nch; ++c) {   // head widths above 64 * V floats
+      const int i = lane + c * 64, e = min(i, n - 1) * V;
+      const float t = Vec::ld(q + base + e).dot(Vec::ld(kr + e));
+      part += i < n ? t : 0.f;
+    }
+    const float sj = wave_sum(part);
+    s = lane == j ? sj : s;
+  }
+  const float m = wave_max(s);
+  const float ex = lane < Tk ? __expf(s - m) : 0.f;
+  const float pr = ex / wave_sum(ex);
+  for (int c = 0; c < nch; ++c) {
+    const int i = lane + c * 64, e = min(i, n - 1) * V;
+    Vec acc = {};
+#pragma unroll 4
+    for (int j = 0; j < Tk; ++j) acc.axpy(__shfl(pr, j, 64), Vec::ld(vc + j * slab + base + e));
+    if (i < n) acc.st(o, base + e, p16);
+  }
+}
+
+extern "C" int vptr_tattn_step(const float* q, const float* kcache, const float* vcache, float* o, int rows, int Tk, int Tcap,
+                               int C, int nh, int p16, vptr_stream_t stream) {
+  VPTR_CHECK(rows > 0 && Tcap > 0 && C > 0 && nh > 0, "tattn_step: bad arguments");
+  VPTR_CHECK(Tk >= 1 && Tk <= Tcap, "tattn_step: Tk = %d outside 1 .. Tcap = %d", Tk, Tcap);
+  VPTR_CHECK(Tk <= ATT_MAXT, "tattn_step: Tk must be <= %d (got %d)", ATT_MAXT, Tk);
+  VPTR_CHECK(C % nh == 0, "tattn_step: embed_dim must be divisible by num_heads");
+  if (p16) VPTR_CHECK(C % 16 == 0, "tattn_step: P16 outputs need C %% 16 == 0 (got %d)", C);
+  const int64_t grid = (int64_t)cdiv(rows, 8) * 8 * nh;
+  VPTR_CHECK(grid <= 0x7fffffff, "tattn_step: too many (row, head) pairs");
+  if ((C / nh) % 2 == 0)
+    tattn_step_kernel<2><<<dim3((unsigned)grid), 64, 0, (hipStream_t)stream>>>(q, kcache, vcache, o, rows, Tk, C, nh, p16);
+  else
+    tattn_step_kernel<1><<<dim3((unsigned)grid), 64, 0, (hipStream_t)stream>>>(q, kcache, vcache, o, rows, Tk, C, nh, p16);
+  VPTR_LAUNCH_CHECK();
+  return 0;
+}
+
 __global__ __launch_bounds__(64) void tattn_bwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                        const float* __restrict__ v, const float* __restrict__ dout,
                                                        float* __restrict__ dq, float* __restrict__ dk, float* __restrict__ dv,

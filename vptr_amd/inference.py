@@ -17,6 +17,8 @@ The reference defines them in Test_VPTR.ipynb cell 5 and train_FAR.py:103-125; t
                                 prediction on, ONE decoder pass at the end; also returns the re-predicted past frames.
 
 Everything runs under no_grad through the same HIP kernels as training (eval mode: dropout / DropPath off).
+`far_rollout(kv_cache=True)` feeds the transformer one new frame per step against cached temporal-attention keys / values
+(`VPTRFormerFAR.forward_cached`, the `vptr_tattn_step` kernel) instead of re-running it over the whole window.
 """
 import torch
 
@@ -65,11 +67,21 @@ def nar_bair_2_to_28(enc, dec, T, past):
 
 
 @torch.no_grad()
-def far_rollout(enc, dec, T, past, num_pred, mode="train"):
+def far_rollout(enc, dec, T, past, num_pred, mode="train", kv_cache=False):
     """mode 'RIP' / 'RIL': past (N,Tp,C,H,W) -> predicted future frames (N,num_pred,C,H,W).
-    mode 'train': -> (pred_past_frames (N,Tp-1,...), pred_future_frames (N,num_pred,...)) exactly as FAR_show_sample's test phase."""
+    mode 'train': -> (pred_past_frames (N,Tp-1,...), pred_future_frames (N,num_pred,...)) exactly as FAR_show_sample's test phase.
+
+    kv_cache=True runs the transformer through `VPTRFormerFAR.forward_cached`: the past features are one prefill pass, every later
+    feature is ONE frame against the cached temporal-attention keys / values instead of a pass over the whole window (in eval mode a
+    frame's activations depend on earlier frames only, through the causal temporal attention, so the outputs are those of the full
+    passes; the two paths run different attention kernels and agree to rounding, not bitwise).  'train': the per-frame outputs are
+    collected and decoded once -- the tensor the last full pass returns.  'RIP' / 'RIL': cached while the window only grows; from
+    the first step at which the window slides, every position (hence every frame's activations) changes and nothing in the cache is
+    reusable, so the rest of the rollout recomputes the slid window as kv_cache=False does."""
     T.eval()
     past_feats = enc(past)
+    if kv_cache:
+        return _far_rollout_cached(enc, dec, T, past_feats, num_pred, mode)
     pred_feats = T(past_feats)
     if mode == "train":
         input_feats = past_feats
@@ -95,4 +107,34 @@ def far_rollout(enc, dec, T, past, num_pred, mode="train"):
         frame = dec(pred_feats[:, -1:])
         frames.append(frame)
         newest = enc(frame) if mode == "RIP" else pred_feats[:, -1:]
+    return torch.cat(frames, dim=1)
+
+
+def _far_rollout_cached(enc, dec, T, past_feats, num_pred, mode):
+    """far_rollout(kv_cache=True) after the encoder pass"""
+    if mode not in ("train", "RIP", "RIL"):
+        raise ValueError("far_rollout: mode must be 'train', 'RIP' or 'RIL'")
+    cache = T.init_cache(past_feats.shape[0], past_feats.device)
+    out = T.forward_cached(past_feats, cache)      # prefill: the outputs of all Tp past frames
+    newest = out[:, -1:]
+    if mode == "train":
+        outs = [out]
+        for i in range(num_pred - 1):
+            newest = T.forward_cached(newest if i == 0 else enc(dec(newest)), cache)
+            outs.append(newest)
+        frames = dec(torch.cat(outs, dim=1))
+        return frames[:, :-num_pred], frames[:, -num_pred:]
+    horizon = T.num_future_frames
+    frames = [dec(newest)]
+    window = past_feats
+    slid = False
+    for i in range(1, num_pred):
+        window = torch.cat([window, newest], dim=1)
+        if i > 1 and i >= horizon:
+            window = window[:, 1:]
+            slid = True                            # the cache is dead from here on: positions shifted under every cached frame
+        last = T(window)[:, -1:] if slid else T.forward_cached(newest, cache)
+        frame = dec(last)
+        frames.append(frame)
+        newest = enc(frame) if mode == "RIP" else last
     return torch.cat(frames, dim=1)

@@ -277,14 +277,15 @@ class MlpDWBN(nn.Module):
 
 
 def _mha_tokens(mha, q_in, k_in, v_in, residual, Nb, Tq, Tk, HW, causal, p_attn, site, out_dropout=0.0, out_site=0,
-                rowscale=None, rs_div=1, rs_mod=1, merge_v_grad=False, x_p16=False, kv_acc=None):
+                rowscale=None, rs_div=1, rs_mod=1, merge_v_grad=False, x_p16=False, kv_acc=None, kv_out=None):
     """Stock nn.MultiheadAttention (packed in_proj) over time on token-major inputs (VidHRFormer_modules.py:79-84).
-    merge_v_grad: q_in is k_in = v_in + a table that needs no gradient, so the three input gradients may be returned as one."""
+    merge_v_grad: q_in is k_in = v_in + a table that needs no gradient, so the three input gradients may be returned as one.
+    kv_out: see ops.proj_temporal_attention."""
     C, nh = mha.embed_dim, mha.num_heads
     w, b = mha.in_proj_weight, mha.in_proj_bias
     P = ops.p16_ok(C)
     o = ops.proj_temporal_attention(q_in, k_in, v_in, w[:C], b[:C], w[C:2 * C], b[C:2 * C], w[2 * C:], b[2 * C:], Nb, Tq, Tk, HW, nh,
-                                    causal, p_attn, site, merge_v_grad=merge_v_grad, x_p16=x_p16, o_p16=P, kv_acc=kv_acc)
+                                    causal, p_attn, site, merge_v_grad=merge_v_grad, x_p16=x_p16, o_p16=P, kv_acc=kv_acc, kv_out=kv_out)
     return ops.linear(o, mha.out_proj.weight, mha.out_proj.bias, residual=residual, dropout_p=out_dropout, site=out_site,
                       rowscale=rowscale, rs_div=rs_div, rs_mod=rs_mod, x_p16=P)
 
@@ -316,8 +317,9 @@ class VidHRFormerBlockEnc(nn.Module):
         self.drop_path_p = drop_path
         self._site = 0
 
-    def forward_tokens(self, x, g, lw_pos, tpos):
-        """x [N*T*H*W, C]; tpos (T, C)."""
+    def forward_tokens(self, x, g, lw_pos, tpos, kv_out=None):
+        """x [N*T*H*W, C]; tpos (T, C).  kv_out: optional callable(k, v) that receives the temporal attention's projected keys and
+        values (the prefill of a decoding cache, see step_tokens)."""
         HW = g.H * g.W
         p = self.dropout if self.training else 0.0
         s = self._site
@@ -337,13 +339,42 @@ class VidHRFormerBlockEnc(nn.Module):
         u, uq, xr = ops.layernorm(x, self.norm3.weight, self.norm3.bias, tab=tpos, tab_div=HW, tab_mod=g.T, eps=self.norm3.eps,
                                   passthrough=True, out_p16=P)
         x = _mha_tokens(self.temporal_MHSA, uq, uq, u, xr, g.N, g.T, g.T, HW, self.far, p, s + 3, out_dropout=p, out_site=s + 4,
-                        merge_v_grad=not tpos.requires_grad, x_p16=P)
+                        merge_v_grad=not tpos.requires_grad, x_p16=P, kv_out=kv_out)
         u, xr = ops.layernorm(x, self.norm4.weight, self.norm4.bias, eps=self.norm4.eps, passthrough=True, out_p16=P)
         if P and ops.config.fused_mlp:   # one autograd node; linear2's input gradient applies GELU' and the dropout mask in its epilogue
             return ops.mlp(u, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, residual=xr, dropout_p=p,
                            site1=s + 5, site2=s + 6, x_p16=True)
         h = ops.linear(u, self.linear1.weight, self.linear1.bias, act=ops.ACT_GELU, dropout_p=p, site=s + 5, x_p16=P, out_p16=P)
         return ops.linear(h, self.linear2.weight, self.linear2.bias, residual=xr, dropout_p=p, site=s + 6, x_p16=P)
+
+    def step_tokens(self, x, g1, lw_pos, tpos_t, kc, vc, t):
+        """One KV-cached decoding step (far=True, eval mode, no grad): x [N*H*W, C] are the tokens of frame t alone, g1 = Geom(N, 1, H, W),
+        tpos_t = temporal_pos[t:t+1], kc / vc [Tcap, N*H*W, C] this layer's time-major key / value cache holding frames 0 .. t-1.
+        Every sub-layer but the causal temporal attention is frame-local in eval mode, so the sequence is forward_tokens' on one frame;
+        the temporal attention projects frame t into slot t of the cache and attends over slots 0 .. t (ops.proj_temporal_attention_step).
+        Returns frame t's tokens exactly as row block t of forward_tokens over frames 0 .. t."""
+        if self.training or not self.far:
+            raise RuntimeError("step_tokens: KV-cached decoding needs a far=True block in eval mode")
+        HW = g1.H * g1.W
+        P = ops.p16_ok(self.embed_dim, self.linear1.weight.shape[0])
+        Pw = P and self.SLMHSA.rpe
+        Pf = P and self.SpatialFFN.p16_in_ok()
+        u, xr = ops.layernorm(x, self.norm1.weight, self.norm1.bias, eps=self.norm1.eps, passthrough=True, out_p16=Pw)
+        x = self.SLMHSA.forward_tokens(u, u, xr, g1, lw_pos, 0, x_p16=Pw)
+        u, xr = ops.layernorm(x, self.norm2.weight, self.norm2.bias, eps=self.norm2.eps, passthrough=True, out_p16=Pf)
+        x = self.SpatialFFN.forward_tokens(u, xr, g1, 0, x_p16=Pf)
+        u, uq, xr = ops.layernorm(x, self.norm3.weight, self.norm3.bias, tab=tpos_t, tab_div=HW, tab_mod=1, eps=self.norm3.eps,
+                                  passthrough=True, out_p16=P)
+        mha = self.temporal_MHSA
+        C, w, b = mha.embed_dim, mha.in_proj_weight, mha.in_proj_bias
+        o = ops.proj_temporal_attention_step(uq, u, w[:C], b[:C], w[C:2 * C], b[C:2 * C], w[2 * C:], b[2 * C:], kc, vc, t, mha.num_heads,
+                                             x_p16=P, o_p16=P)
+        x = ops.linear(o, mha.out_proj.weight, mha.out_proj.bias, residual=xr, x_p16=P)
+        u, xr = ops.layernorm(x, self.norm4.weight, self.norm4.bias, eps=self.norm4.eps, passthrough=True, out_p16=P)
+        if P and ops.config.fused_mlp:
+            return ops.mlp(u, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, residual=xr, x_p16=True)
+        h = ops.linear(u, self.linear1.weight, self.linear1.bias, act=ops.ACT_GELU, x_p16=P, out_p16=P)
+        return ops.linear(h, self.linear2.weight, self.linear2.bias, residual=xr, x_p16=P)
 
 
 class VidHRFormerEncoder(nn.Module):
@@ -353,9 +384,18 @@ class VidHRFormerEncoder(nn.Module):
         self.num_layers = num_layers
         self.norm = norm
 
-    def forward_tokens(self, x, g, lw_pos, tpos):
-        for layer in self.layers:
-            x = layer.forward_tokens(x, g, lw_pos, tpos)
+    def forward_tokens(self, x, g, lw_pos, tpos, kv_out=None):
+        """kv_out: optional list of one callable(k, v) per layer (VidHRFormerBlockEnc.forward_tokens)"""
+        for i, layer in enumerate(self.layers):
+            x = layer.forward_tokens(x, g, lw_pos, tpos) if kv_out is None else layer.forward_tokens(x, g, lw_pos, tpos, kv_out[i])
+        if self.norm is not None:
+            x = ops.layernorm(x, self.norm.weight, self.norm.bias, eps=self.norm.eps)
+        return x
+
+    def step_tokens(self, x, g1, lw_pos, tpos_t, ks, vs, t):
+        """one KV-cached frame through every layer (VidHRFormerBlockEnc.step_tokens); ks / vs: the per-layer caches"""
+        for layer, kc, vc in zip(self.layers, ks, vs):
+            x = layer.step_tokens(x, g1, lw_pos, tpos_t, kc, vc, t)
         if self.norm is not None:
             x = ops.layernorm(x, self.norm.weight, self.norm.bias, eps=self.norm.eps)
         return x
@@ -550,7 +590,8 @@ class VidHRFormerFAR(nn.Module):
                                 dim_feedforward, far=True, rpe=rpe), num_encoder_layer, nn.LayerNorm(embed_dim))
         _assign_sites(self)
 
-    def forward(self, input_feat, local_window_pos_embed, temporal_pos_embed):
+    def forward(self, input_feat, local_window_pos_embed, temporal_pos_embed, kv_out=None):
+        """kv_out: optional list of one callable(k, v) per layer, handed that layer's projected temporal-attention keys / values"""
         N, T, C, H, W = input_feat.shape
         plan = self.__dict__.setdefault("_dp", {}).setdefault((self.training, N, T), _DropPathPlan())
         _dp_plan[0] = plan
@@ -559,10 +600,70 @@ class VidHRFormerFAR(nn.Module):
         arena.__enter__()
         try:
             x = ops.nchw_to_tokens(input_feat.reshape(N * T, C, H, W))
-            x = self.encoder.forward_tokens(x, Geom(N, T, H, W), local_window_pos_embed, temporal_pos_embed[:T])
+            x = self.encoder.forward_tokens(x, Geom(N, T, H, W), local_window_pos_embed, temporal_pos_embed[:T], kv_out)
             out = ops.tokens_to_nchw(x, N * T, C, H, W, relu=True).reshape(N, T, C, H, W)
         finally:
             arena.__exit__(None, None, None)
             plan.end()
             _dp_plan[0] = None
         return out
+
+    def init_cache(self, N, Tcap, device):
+        return FARCache(self.num_encoder_layer, Tcap, N, self.H, self.W, self.embed_dim, device)
+
+    @torch.no_grad()
+    def forward_cached(self, feats, local_window_pos_embed, temporal_pos_embed, cache):
+        """feats (N,Tn,C,H,W): the frames at positions cache.len .. cache.len+Tn-1 -> their outputs (N,Tn,C,H,W), equal to the same
+        frames of forward() over the whole sequence so far (every sub-layer but the causal temporal attention is frame-local in eval
+        mode, so a frame's activations depend on earlier frames through the cached keys / values alone).  Several frames at once only
+        into an empty cache (prefill: the ordinary causal pass, whose projected keys / values are copied into the cache, one strided
+        copy per layer and tensor); afterwards one frame per call (VidHRFormerBlockEnc.step_tokens)."""
+        if self.training:
+            raise ValueError("forward_cached: KV-cached decoding is eval-only (dropout / DropPath must be off)")
+        if feats.dim() != 5:
+            raise ValueError("forward_cached: feats must be (N, Tn, C, H, W)")
+        N, Tn, C, H, W = feats.shape
+        if (N, H, W, C) != (cache.N, cache.H, cache.W, cache.C):
+            raise ValueError("forward_cached: feats (N=%d, C=%d, %dx%d) do not match the cache (N=%d, C=%d, %dx%d)"
+                             % (N, C, H, W, cache.N, cache.C, cache.H, cache.W))
+        if len(cache.k) != len(self.encoder.layers) or cache.Tcap > temporal_pos_embed.shape[0]:
+            raise ValueError("forward_cached: the cache was built for another model")
+        if Tn < 1 or cache.len + Tn > cache.Tcap:
+            raise ValueError("forward_cached: %d cached + %d new frames exceed the cache's %d" % (cache.len, Tn, cache.Tcap))
+        if cache.len > 0 and Tn != 1:
+            raise ValueError("forward_cached: a non-empty cache takes one frame per call (got %d)" % Tn)
+        HW = H * W
+        if Tn > 1:
+            def export(kc, vc):
+                def hook(k, v):   # (n, t, p) rows -> time-major slots
+                    kc[:Tn].view(Tn, N, HW, C).copy_(k.view(N, Tn, HW, C).transpose(0, 1))
+                    vc[:Tn].view(Tn, N, HW, C).copy_(v.view(N, Tn, HW, C).transpose(0, 1))
+                return hook
+            out = self.forward(feats, local_window_pos_embed, temporal_pos_embed, [export(kc, vc) for kc, vc in zip(cache.k, cache.v)])
+            cache.len = Tn
+            return out
+        t = cache.len
+        with ops.zero_arena(_ln_ffn_stats_floats(self.encoder, N), feats.device):
+            x = ops.nchw_to_tokens(feats.reshape(N, C, H, W))
+            x = self.encoder.step_tokens(x, Geom(N, 1, H, W), local_window_pos_embed, temporal_pos_embed[t:t + 1], cache.k, cache.v, t)
+            out = ops.tokens_to_nchw(x, N, C, H, W, relu=True).reshape(N, 1, C, H, W)
+        cache.len = t + 1
+        return out
+
+
+class FARCache:
+    """Key / value cache of VidHRFormerFAR.forward_cached: per layer the temporal attention's projected keys and values of every frame
+    fed so far, `k[l]`, `v[l]`: [Tcap, N*H*W, C] fp32, TIME-MAJOR (frame t is one contiguous [N*H*W, C] slab, which a decoding step's
+    projection GEMM writes in place); `len` frames are valid.  Owns layers * 2 * Tcap * N*H*W * C * 4 bytes (12 layers, 30 frames,
+    batch 16 of 8x8 x 528 features: 1.6 GB)."""
+
+    def __init__(self, layers, Tcap, N, H, W, C, device):
+        self.Tcap, self.N, self.H, self.W, self.C, self.len = int(Tcap), int(N), int(H), int(W), int(C), 0
+        self.k = [torch.empty((self.Tcap, N * H * W, C), device=device, dtype=torch.float32) for _ in range(layers)]
+        self.v = [torch.empty((self.Tcap, N * H * W, C), device=device, dtype=torch.float32) for _ in range(layers)]
+
+    def reset(self):
+        self.len = 0
+
+    def nbytes(self):
+        return sum(t.numel() * 4 for t in self.k + self.v)

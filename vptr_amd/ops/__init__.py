@@ -37,7 +37,7 @@ from .norm import (  # noqa: F401
 )
 from .attention import (  # noqa: F401
     _winattn_workspace, _WinAttnFn, _WinAttnFn_apply, window_attention, _TAttnFn, _TAttnFn_apply, temporal_attention, KVGradAccum,
-    _ProjAttnFn, _ProjAttnFn_apply, _proj_attention, proj_window_attention, proj_temporal_attention, _TSAttnFn,
+    _ProjAttnFn, _ProjAttnFn_apply, _proj_attention, proj_window_attention, proj_temporal_attention, proj_temporal_attention_step, _TSAttnFn,
     temporal_spatial_window_attention,
 )
 from .convffn import (  # noqa: F401

@@ -169,7 +169,7 @@ class _ProjAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xq, xk, xv, Wq, bq, Wk, bk, Wv, bv, table, rel_index, kind, geom, nh, p, site, same_qk, same_v, merge_v, x_p16, o_p16,
-                kv_acc=None):
+                kv_acc=None, kv_out=None):
         _lib.require_cuda(xq, xk, xv, Wq)
         ctx.kv_acc = kv_acc
         if kv_acc is not None:
@@ -207,6 +207,8 @@ class _ProjAttnFn(torch.autograd.Function):
         else:
             gemm_raw(xq, Wq, q, Mq, N, K, 0, 0, bias=bq, alpha=alpha)
             gemm_raw(xk, Wk, k, Mk, N, K, 0, 0, bias=bk, batch_extra=[(xv, Wv, v, bv, 1.0)])
+        if kv_out is not None:   # the projected keys / values as the attention reads them (the decoding cache's prefill)
+            kv_out(k, v)
         o = torch.empty_like(q)
         ctx.seed = seed_tensor(dev) if p > 0 else None
         if kind == 0:
@@ -309,18 +311,18 @@ class _ProjAttnFn(torch.autograd.Function):
                 dxk = acc.k if dxk is None else dxk + acc.k
                 dxv = acc.v if dxv is None else dxv + acc.v
                 acc.k = acc.v = None
-        return (dxq, dxk, dxv, dWq, dbq, dWk, dbk, dWv, dbv, dtable) + (None,) * 12
+        return (dxq, dxk, dxv, dWq, dbq, dWk, dbk, dWv, dbv, dtable) + (None,) * 13
 
 
 _ProjAttnFn_apply = _direct_apply(_ProjAttnFn)
 
 
 def _proj_attention(xq, xk, xv, Wq, bq, Wk, bk, Wv, bv, table, rel_index, kind, geom, nh, p, site, merge_v_grad, x_p16=False, o_p16=False,
-                    kv_acc=None):
+                    kv_acc=None, kv_out=None):
     same_qk = xk is xq
     same_v = same_qk and xv is xq
     return _ProjAttnFn_apply(xq, xk, xv, Wq, bq, Wk, bk, Wv, bv, table, rel_index, kind, geom, int(nh), float(p), int(site),
-                             same_qk, same_v, bool(merge_v_grad) and same_qk, bool(x_p16), bool(o_p16), kv_acc)
+                             same_qk, same_v, bool(merge_v_grad) and same_qk, bool(x_p16), bool(o_p16), kv_acc, kv_out)
 
 
 def proj_window_attention(xqk, xv, Wq, bq, Wk, bk, Wv, bv, table, rel_index, B, H, W, nh, ws, dropout_p=0.0, site=0,
@@ -332,11 +334,69 @@ def proj_window_attention(xqk, xv, Wq, bq, Wk, bk, Wv, bv, table, rel_index, B, 
 
 
 def proj_temporal_attention(q_in, k_in, v_in, Wq, bq, Wk, bk, Wv, bv, Nb, Tq, Tk, HW, nh, causal=False, dropout_p=0.0, site=0,
-                            merge_v_grad=False, x_p16=False, o_p16=False, kv_acc=None):
+                            merge_v_grad=False, x_p16=False, o_p16=False, kv_acc=None, kv_out=None):
     """Temporal attention INCLUDING its q/k/v projections; q_in [(n,tq,p), C], k_in, v_in [(n,tk,p), C].
-    kv_acc: a KVGradAccum shared by every attention that reads the same k_in / v_in tensors (gradients summed inside the GEMMs)."""
+    kv_acc: a KVGradAccum shared by every attention that reads the same k_in / v_in tensors (gradients summed inside the GEMMs).
+    kv_out: optional callable(k, v) handed the projected [(n,tk,p), C] keys and values (read-only) before the attention core runs."""
     return _proj_attention(q_in, k_in, v_in, Wq, bq, Wk, bk, Wv, bv, None, None, 1,
-                           (int(Nb), int(Tq), int(Tk), int(HW), int(bool(causal))), nh, dropout_p, site, merge_v_grad, x_p16, o_p16, kv_acc)
+                           (int(Nb), int(Tq), int(Tk), int(HW), int(bool(causal))), nh, dropout_p, site, merge_v_grad, x_p16, o_p16, kv_acc, kv_out)
+
+
+class _SlotPtr:
+    """data_ptr() of one [rows, C] slot of a time-major cache, without building a view tensor per step"""
+    __slots__ = ("p",)
+
+    def __init__(self, cache, t):
+        self.p = cache.data_ptr() + t * cache.stride(0) * 4
+
+    def data_ptr(self):
+        return self.p
+
+
+def proj_temporal_attention_step(xq, xv, Wq, bq, Wk, bk, Wv, bv, kcache, vcache, t, nh, x_p16=False, o_p16=False):
+    """One KV-cached decoding step of the causal temporal attention INCLUDING its q/k/v projections (inference only).
+    xq = LayerNorm output + temporal-position row of frame t (queries and keys), xv = LayerNorm output (values), both [rows, C]
+    (P16 tensors with x_p16); kcache, vcache [Tcap, rows, C] fp32, time-major.  The three projections run as one batched GEMM
+    launch whose key / value outputs ARE slots kcache[t] / vcache[t] (contiguous slabs: no append copy); then one vptr_tattn_step
+    over slots 0 .. t.  Returns the [rows, C] heads before out_proj (a P16 tensor with o_p16)."""
+    if torch.is_grad_enabled() and any(a is not None and a.requires_grad for a in (xq, xv, Wq, bq, Wk, bk, Wv, bv, kcache, vcache)):
+        raise RuntimeError("proj_temporal_attention_step is inference-only: call it under torch.no_grad()")
+    _lib.require_cuda(xq, xv, Wq, kcache, vcache)
+    xq, xv = _c(xq), _c(xv)
+    Wq, Wk, Wv = _c(Wq), _c(Wk), _c(Wv)
+    M, K = xq.shape
+    N = Wq.shape[0]
+    t = int(t)
+    for c in (kcache, vcache):
+        if c.dtype != torch.float32 or c.dim() != 3 or tuple(c.shape[1:]) != (M, N) or not c.is_contiguous():
+            raise RuntimeError("proj_temporal_attention_step: the caches must be contiguous fp32 [Tcap, %d, %d] tensors" % (M, N))
+    Tcap = kcache.shape[0]
+    if vcache.shape[0] != Tcap or not 0 <= t < Tcap:
+        raise RuntimeError("proj_temporal_attention_step: slot %d outside a cache of %d frames" % (t, Tcap))
+    if xv.shape != xq.shape:
+        raise RuntimeError("proj_temporal_attention_step: xq and xv differ in shape")
+    alpha = float(N // nh) ** -0.5
+    use = p16_ok(K, N)
+    if (x_p16 or o_p16) and not use:
+        raise RuntimeError("attention: P16 operands need the embedding width to be a multiple of 16 (got %d)" % K)
+    q = torch.empty((M, N), device=xq.device, dtype=torch.float32)
+    kt, vt = _SlotPtr(kcache, t), _SlotPtr(vcache, t)
+    if use:
+        if not x_p16:
+            same = xv is xq
+            xq = to_p16(xq)
+            xv = xq if same else to_p16(xv)
+        (Pq, lq, _, _), (Pk, lk, _, _), (Pv, lv, _, _) = weight_planes_for(Wq), weight_planes_for(Wk), weight_planes_for(Wv)
+        if not (lq == lk == lv):
+            raise RuntimeError("attention: q/k/v weight planes with different pitches")
+        gemm_raw(xq, Pq, q, M, N, K, A_P16, B_P16, lda=K, ldb=lq, bias=bq, alpha=alpha,
+                 batch_extra=[(xq, Pk, kt, bk, 1.0), (xv, Pv, vt, bv, 1.0)])
+    else:
+        gemm_raw(xq, Wq, q, M, N, K, 0, 0, bias=bq, alpha=alpha, batch_extra=[(xq, Wk, kt, bk, 1.0), (xv, Wv, vt, bv, 1.0)])
+    o = torch.empty_like(q)
+    check(lib.vptr_tattn_step(ptr(q), ptr(kcache), ptr(vcache), ptr(o), M, t + 1, Tcap, N, int(nh), int(bool(o_p16)), stream()),
+          "vptr_tattn_step")
+    return o
 
 
 class _TSAttnFn(torch.autograd.Function):

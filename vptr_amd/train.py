@@ -720,10 +720,12 @@ class FARTrainer(NARTrainer):
         return self._finish(loss, dict({"T_total": loss.detach(), "T_GDL": l_gdl.detach(), "T_MSE": l_mse.detach()}, **extra), front)
 
     @torch.no_grad()
-    def predict(self, past, num_pred):
-        """Autoregressive test-phase rollout (train_FAR.py:103-125): see vptr_amd.inference.far_rollout."""
+    def predict(self, past, num_pred, kv_cache=False):
+        """Autoregressive test-phase rollout (train_FAR.py:103-125): see vptr_amd.inference.far_rollout (kv_cache: its KV-cached path)."""
         from .inference import far_rollout
-        return far_rollout(self.enc, self.dec, self.T, past, num_pred)
+        return far_rollout(self.enc, self.dec, self.T, past, num_pred, kv_cache=kv_cache)
+
+    rollout = predict
 
 
 class AETrainer:
