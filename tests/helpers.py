@@ -209,3 +209,69 @@ def reflect_fold_ref(dxpad, pad):
         shape[dim] = n
         return torch.zeros(shape, dtype=t.dtype).index_add_(dim, src, t)
     return fold(fold(dxpad, 2), 3)
+
+
+# ---- fp64 reference builders of the deferred-backward op tests (tests/test_09b_deferred_bwd_gpu.py); like the ones above, each is checked on the
+# CPU against an independent closed-form formulation (tests/test_cpu.py)
+def ln_bwd_ref(x, gamma, dy, dy2=None, dx_add=None, eps=1e-5):
+    """backward of LayerNorm(C) as the trainers' backward node runs it (vptr_layernorm_bwd*): fp64 autograd of F.layer_norm on x [rows, C] with the
+    upstream gradient dy + dy2 (dy2: the gradient of the position-added second output), dx_add (the residual gradient that passes through the
+    node) added onto dx.  Returns fp64 dx [rows, C], dgamma, dbeta [C] and the row statistics mean, rstd [rows] of the fp32 x."""
+    import torch.nn.functional as F
+    xr, gr = x.double().requires_grad_(True), gamma.double().requires_grad_(True)
+    br = torch.zeros_like(gr).requires_grad_(True)
+    g = dy.double() if dy2 is None else dy.double() + dy2.double()
+    F.layer_norm(xr, (x.shape[1],), gr, br, eps).backward(g)
+    xd = x.double()
+    dx = xr.grad if dx_add is None else xr.grad + dx_add.double()
+    return {"dx": dx, "dgamma": gr.grad, "dbeta": br.grad, "mean": xd.mean(1), "rstd": (xd.var(1, unbiased=False) + eps).rsqrt()}
+
+
+KINK, KINK_CAP = 1e-3, 5e-3     # the kink rule of tests/test_09_stage1_ops_gpu.py
+
+
+def norm_act_ln_bwd_ref(x, w, b, dy, frames, HW, act, mask=None, keep=1.0, rowscale=None, rs_div=1, rs_mod=1, eps=1e-5):
+    """backward of y = act(LayerNorm((F,H,W))(x) * w + b) * mask / keep * rowscale[(row // rs_div) % rs_mod] (vptr_norm_act_bwd* with
+    per_col = 0) by fp64 autograd.  x, dy, mask: channel-last [frames * HW, F]; w, b: the (F, H, W) affine in the kernels' layout [HW, F]
+    -- a frame's HW x F block holds exactly the elements of its (F, H, W) tensor, so F.layer_norm over the trailing (HW, F) of the
+    channel-last view is the same normalisation and the same elementwise affine.  act: 0 none, 1 GELU (erf form), 2 ReLU; for ReLU the
+    upstream gradient is zeroed where |pre| < KINK * rms(pre) (the returned "dy" is what the kernel must be given, "kink_share" the zeroed
+    share).  Returns fp64 dx [rows, F], dw, db [HW, F], the frame statistics mean, rstd [frames], the pre-activation and dy."""
+    import torch.nn.functional as F
+    rows, Fc = x.shape
+    assert rows == frames * HW and tuple(w.shape) == (HW, Fc)
+    xr = x.double().requires_grad_(True)
+    wr, br = w.double().requires_grad_(True), b.double().requires_grad_(True)
+    pre = F.layer_norm(xr.view(frames, HW, Fc), (HW, Fc), wr, br, eps).reshape(rows, Fc)
+    y = F.gelu(pre) if act == 1 else (torch.relu(pre) if act == 2 else pre)
+    if mask is not None:
+        y = y * mask.double() / keep
+    if rowscale is not None:
+        y = y * rowscale.double()[(torch.arange(rows) // rs_div) % rs_mod][:, None]
+    g, share = dy.double(), 0.0
+    if act == 2:
+        near = pre.detach().abs() < KINK * pre.detach().pow(2).mean().sqrt()
+        share = float(near.double().mean())
+        g = torch.where(near, torch.zeros_like(g), g)
+    y.backward(g)
+    xf = x.double().view(frames, HW * Fc)
+    return {"dx": xr.grad, "dw": wr.grad, "db": br.grad, "mean": xf.mean(1), "rstd": (xf.var(1, unbiased=False) + eps).rsqrt(),
+            "pre": pre.detach(), "dy": g, "kink_share": share}
+
+
+# (frames, HW, F) of the LayerNorm((F,H,W)) backward cases: id -> (deferred call?, frames, HW, F); what each one stresses is said where they run
+NORM_ACT_LN_CASES = {
+    "plain_13x12x20": (False, 13, 12, 20), "plain_70x16x32": (False, 70, 16, 32), "plain_67x64x256": (False, 67, 64, 256),
+    "deferred_64x16x32": (True, 64, 16, 32), "deferred_70x16x32": (True, 70, 16, 32), "deferred_100x4x16": (True, 100, 4, 16),
+    "deferred_66x64x1024": (True, 66, 64, 1024),
+}
+
+
+def norm_act_ln_inputs(case):
+    """the seeded fp32 inputs of one NORM_ACT_LN_CASES entry: x, dy [rows, F], w, b [HW, F] and a DropPath-like row scale [frames] (0 or 1 / 0.8)"""
+    _, frames, HW, Fc = NORM_ACT_LN_CASES[case]
+    seed = 3000 + 10 * sorted(NORM_ACT_LN_CASES).index(case)
+    x, dy = fill.rand_normal((frames * HW, Fc), seed, 2.0) + 0.3, fill.rand_normal((frames * HW, Fc), seed + 1)
+    w, b = fill.rand_normal((HW, Fc), seed + 2).abs() + 0.5, fill.rand_normal((HW, Fc), seed + 3, 0.3)
+    rowscale = (fill.rand_input((frames,), seed + 4) > 0.2).float() / 0.8
+    return x, dy, w, b, rowscale

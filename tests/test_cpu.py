@@ -723,3 +723,90 @@ def test_reflect_fold_ref_is_the_adjoint_of_reflection_padding(H, W, pad):
     g = fill.rand_normal((2, 3, H + 2 * pad, W + 2 * pad), 12).double()
     (ref,) = torch.autograd.grad(F.pad(x, (pad,) * 4, mode="reflect"), x, g)
     assert rel(reflect_fold_ref(g, pad), ref) < 1e-15
+
+
+# ---- the fp64 reference builders of the deferred-backward op tests (tests/test_09b_deferred_bwd_gpu.py) --------------------------------------------
+def _ln_closed_form(g, xhat, wgt, rstd, dims):
+    """rstd * (g*w - mean(g*w) - xhat * mean(g*w*xhat)), the means over `dims`"""
+    gw = g * wgt
+    return rstd * (gw - gw.mean(dims, keepdim=True) - xhat * (gw * xhat).mean(dims, keepdim=True))
+
+
+@pytest.mark.parametrize("with_dy2,with_add", [(True, True), (False, False), (False, True)])
+@pytest.mark.parametrize("rows,C", [(37, 48), (9, 260)])
+def test_ln_bwd_ref_matches_closed_form(rows, C, with_dy2, with_add):
+    """helpers.ln_bwd_ref (autograd of F.layer_norm) == the closed form with explicit statistics, dy2 and dx_add included"""
+    from helpers import ln_bwd_ref
+    x, gamma = fill.rand_normal((rows, C), 21, 2.0) + 0.3, fill.rand_normal((C,), 22).abs() + 0.5
+    dy = fill.rand_normal((rows, C), 23)
+    dy2 = fill.rand_normal((rows, C), 24) if with_dy2 else None
+    add = fill.rand_normal((rows, C), 25) if with_add else None
+    ref = ln_bwd_ref(x, gamma, dy, dy2, add)
+    xd = x.double()
+    mean = xd.sum(1, keepdim=True) / C
+    rstd = 1.0 / torch.sqrt(((xd - mean) ** 2).sum(1, keepdim=True) / C + 1e-5)
+    xhat = (xd - mean) * rstd
+    g = dy.double() + (dy2.double() if with_dy2 else 0.0)
+    dx = _ln_closed_form(g, xhat, gamma.double(), rstd, 1) + (add.double() if with_add else 0.0)
+    assert rel(ref["dx"], dx) < 1e-10
+    assert rel(ref["dgamma"], (g * xhat).sum(0)) < 1e-10 and rel(ref["dbeta"], g.sum(0)) < 1e-10
+    assert rel(ref["mean"], mean[:, 0]) < 1e-10 and rel(ref["rstd"], rstd[:, 0]) < 1e-10
+
+
+@pytest.mark.parametrize("act", [0, 1, 2])
+@pytest.mark.parametrize("p", [0.0, 0.1])
+def test_norm_act_ln_bwd_ref_matches_closed_form(act, p):
+    """helpers.norm_act_ln_bwd_ref (autograd, channel-last [HW, F] affine) == the closed form written in the module's own NCHW layout:
+    statistics over (F, H, W) of a [frames, F, H, W] tensor, affine parameters as (F, H, W), analytic activation derivatives, mask / keep
+    and the per-row scale folded into the upstream gradient (a transposed affine, a mask on the wrong side of the activation or a row
+    scale indexed by frame instead of by row would not agree)"""
+    from helpers import KINK, norm_act_ln_bwd_ref
+    frames, H, W, Fc = 5, 2, 3, 8
+    HW, rows = H * W, frames * H * W
+    x, dy = fill.rand_normal((rows, Fc), 31, 2.0) + 0.3, fill.rand_normal((rows, Fc), 32)
+    w, b = fill.rand_normal((HW, Fc), 33).abs() + 0.5, fill.rand_normal((HW, Fc), 34, 0.3)
+    rs = torch.tensor([1.25, 0.0, 1.25])
+    rs_div, rs_mod = 4, 3                                                # runs of 4 rows: not the frame length
+    mask = (fill.rand_input((rows, Fc), 35) >= p).float() if p > 0 else None
+    ref = norm_act_ln_bwd_ref(x, w, b, dy, frames, HW, act, mask, 1.0 - p, rs, rs_div, rs_mod)
+
+    def nchw(t):
+        return t.double().reshape(-1, H, W, Fc).permute(0, 3, 1, 2)
+    x4, w4, b4 = nchw(x), nchw(w)[0], nchw(b)[0]
+    n = Fc * H * W
+    mean = x4.sum((1, 2, 3), keepdim=True) / n
+    rstd = 1.0 / torch.sqrt(((x4 - mean) ** 2).sum((1, 2, 3), keepdim=True) / n + 1e-5)
+    xhat = (x4 - mean) * rstd
+    pre = xhat * w4 + b4
+    if act == 1:
+        slope = 0.5 * (1.0 + torch.erf(pre / 2 ** 0.5)) + pre * torch.exp(-0.5 * pre * pre) / (2 * np.pi) ** 0.5
+    else:
+        slope = (pre > 0).double() if act == 2 else torch.ones_like(pre)
+    g = nchw(dy)
+    if act == 2:
+        g = torch.where(pre.abs() < KINK * (pre ** 2).mean().sqrt(), torch.zeros_like(g), g)
+    scale = nchw(rs.double()[(torch.arange(rows) // rs_div) % rs_mod][:, None].expand(rows, Fc))
+    if p > 0:
+        scale = scale * nchw(mask) / (1.0 - p)
+    g = g * scale * slope
+    dx = _ln_closed_form(g, xhat, w4, rstd, (1, 2, 3))
+
+    def cl(t):      # [.., F, H, W] -> channel-last rows
+        return t.permute(*range(t.dim() - 3), -2, -1, -3).reshape(-1, Fc)
+    assert rel(ref["dx"], cl(dx)) < 1e-10
+    assert rel(ref["dw"], cl((g * xhat).sum(0))) < 1e-10 and rel(ref["db"], cl(g.sum(0))) < 1e-10
+    assert rel(ref["mean"], mean.reshape(-1)) < 1e-10 and rel(ref["rstd"], rstd.reshape(-1)) < 1e-10
+    assert rel(ref["pre"], cl(pre)) < 1e-10
+
+
+def test_deferred_bwd_cases_input_conditions():
+    """conditions on the seeded inputs of the LayerNorm((F,H,W)) backward cases that need no GPU: the share of ReLU pre-activations next to the
+    kink stays under the cap of the kink rule, and the DropPath-like row scale has both dropped and kept frames"""
+    from helpers import KINK, KINK_CAP, NORM_ACT_LN_CASES, norm_act_ln_inputs
+    for case in sorted(NORM_ACT_LN_CASES):
+        _, frames, HW, Fc = NORM_ACT_LN_CASES[case]
+        x, dy, w, b, rs = norm_act_ln_inputs(case)
+        pre = torch.nn.functional.layer_norm(x.double().view(frames, HW, Fc), (HW, Fc), w.double(), b.double(), 1e-5)
+        share = float((pre.abs() < KINK * pre.pow(2).mean().sqrt()).double().mean())
+        assert share <= KINK_CAP, (case, share)
+        assert 0 < int((rs == 0).sum()) < frames, case
