@@ -1,5 +1,5 @@
 """Stand-alone timing of the conv-FFN forward chain at the K64 step's shape (GPU box): the fused norm1 + GELU + depthwise launch
-(vptr_dwconv3x3_norm_fwd; VPTR_DWN_LDS / VPTR_DWN_DBG select the kernel and its elimination variants, read once per process) against the
+(vptr_dwconv3x3_norm_fwd: the LDS-slab kernel at this shape) against the
 two launches it replaces, plus LayerNorm(528) forward with fp32 and P16 output.  python tools/dwn_probe.py [--reps 50]"""
 import argparse
 import os
@@ -62,14 +62,12 @@ def dw_only():
     check(lib.vptr_dwconv3x3_fwd(ptr(a), ptr(w9), ptr(b9), ptr(y), frames, H, W, F, ptr(st2), stream()), "dwconv")
 
 
-env = {k: os.environ[k] for k in ("VPTR_DWN_LDS", "VPTR_DWN_DBG") if k in os.environ}
-print("env %s: fused %.1f us   fused without fp16 side copy %.1f us   norm_act_fwd %.1f us + dwconv3x3_fwd %.1f us" % (
-    env, timed(fused), timed(fused_noah), timed(norm_only), timed(dw_only)))
-if not env:
-    xs = torch.randn(10240, 528, device=dev)
-    g, bb = torch.rand(528, device=dev) + 0.5, torch.randn(528, device=dev)
-    o, m2, r2 = torch.empty_like(xs), torch.empty(10240, device=dev), torch.empty(10240, device=dev)
-    for p16 in (0, 1):
-        t = timed(lambda: check(lib.vptr_layernorm_fwd(ptr(xs), ptr(g), ptr(bb), ptr(o), None, None, 1, 1, ptr(m2), ptr(r2), 10240, 528, 1e-5, p16,
-                                                       stream()), "ln"))
-        print("layernorm_fwd 10240 x 528, p16 = %d: %.1f us" % (p16, t))
+print("fused %.1f us   fused without fp16 side copy %.1f us   norm_act_fwd %.1f us + dwconv3x3_fwd %.1f us" % (
+    timed(fused), timed(fused_noah), timed(norm_only), timed(dw_only)))
+xs = torch.randn(10240, 528, device=dev)
+g, bb = torch.rand(528, device=dev) + 0.5, torch.randn(528, device=dev)
+o, m2, r2 = torch.empty_like(xs), torch.empty(10240, device=dev), torch.empty(10240, device=dev)
+for p16 in (0, 1):
+    t = timed(lambda: check(lib.vptr_layernorm_fwd(ptr(xs), ptr(g), ptr(bb), ptr(o), None, None, 1, 1, ptr(m2), ptr(r2), 10240, 528, 1e-5, p16,
+                                                   stream()), "ln"))
+    print("layernorm_fwd 10240 x 528, p16 = %d: %.1f us" % (p16, t))

@@ -22,16 +22,6 @@ def _norm_act_backward(dy, x, w, b, mean, rstd, rowscale, HW, per_col, act, cons
     dw, db = (sw, sb) if in_slab else (_bw_zeros(w.shape, w.device), _bw_zeros(b.shape, b.device))
     frames = rows // HW
     scratch = torch.empty((max(2 * F, 2 * frames * (1 + 4 * ((HW * F // 4 + 255) // 256))),), device=x.device, dtype=torch.float32)
-    ncoop = lib.vptr_norm_act_bwd_coop_partials(rows, F, HW) if (in_slab and config.defer_ln_param_grads and not per_col and config.norm_coop) else 0
-    if ncoop > 0:
-        # LayerNorm((F,H,W)): both phases in ONE cooperative pass over (dy, x) -- the workgroups of a 10-frame chunk exchange the frames' sums through
-        # a zeroed workspace line per frame (csrc/norm.hip norm_act_bwd_coop_kernel); affine gradients as per-chunk partial sums like below
-        part = torch.empty((ncoop, 2, HW * F), device=x.device, dtype=torch.float32)
-        ws = _bw_zeros(((frames + 1) * 32,), x.device)
-        check(lib.vptr_norm_act_bwd_coop(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(w), ptr(b), ptr(dx), ptr(ws), rows, F, HW, act, p, ptr(seed), site,
-                                         ptr(rowscale), rs_div, rs_mod, int(dx_p16), ptr(part), stream()), "vptr_norm_act_bwd_coop")
-        defer_partial_reduce(part, sw, sb, ncoop, HW * F)
-        return dx, None, None
     nparts = lib.vptr_norm_act_bwd_partials(rows, F, HW, int(per_col)) if (in_slab and config.defer_ln_param_grads) else 0
     if nparts > 0:
         # affine gradients with an in-place destination: per-chunk partial sums, added by the backward pass's one reduction launch
@@ -173,7 +163,7 @@ def norm_dwconv_ok(rows, HW, F, H, W):
     # clip: 175 against 65 + 86) the two-launch form is faster; VPTR_FUSED_NORM_DW=2 forces the fused launch wherever it is valid
     if config.fused_norm_dwconv_mode != 2 and (H * W > 64 or rows * F * 4 > (128 << 20)):
         return False
-    return (config.fused_norm_dwconv and not config.deterministic and frame_stats_ok(rows, HW, F, W) and W % 2 == 0 and W2 >= 1 and 16 % W2 == 0
+    return (config.fused_norm_dwconv_mode != 0 and not config.deterministic and frame_stats_ok(rows, HW, F, W) and W % 2 == 0 and W2 >= 1 and 16 % W2 == 0
             and H * W == HW)
 
 
