@@ -541,6 +541,21 @@ int vptr_droppath_scales(const float* keep, float* out, int nreq, int maxcount, 
                          vptr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Evaluation: per-frame PSNR / summed squared error / SSIM of predicted frames (utils/metrics.py:12-106).
+ * ---------------------------------------------------------------------------------------------- */
+/* pred, gt: [frames][C][H][W] in the model's normalised range; mean, std: DEVICE [C]; every element is renormalised on load,
+ * x' = x * std[c] + mean[c] (VidReNormalize), and with clamp == 1 clamped to [0, 1] afterwards.  out: [frames][3] =
+ *   { -10 log10(sse / (C H W) / data_range^2 + 1e-8),  sse = sum over C, H, W of (x' - y')^2,  mean over C, H, W of the SSIM map }
+ * (SSIM: 11-tap Gaussian window, sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2, per-channel statistics -- SSIM(size_average=False)).
+ * scratch: frames * C * ceil(H / 16) * 2 floats.  Any H >= 1, 1 <= W <= 256 (also images smaller than the window).  Two launches, no
+ * atomics, no memset: bit-reproducible. */
+int vptr_frame_metrics(const float* pred, const float* gt, const float* mean, const float* std, float* scratch, float* out, int frames,
+                       int C, int H, int W, int clamp, float data_range, vptr_stream_t stream);
+/* acc[t][k] += sum over n of per_frame[n * T + t][k]; per_frame: [N * T][3] fp32 (the `out` above), acc: [T][3] fp64.  One launch,
+ * fixed summation order: the running per-time-index sums of an evaluation stay on the device. */
+int vptr_frame_metrics_accumulate(const float* per_frame, double* acc, int N, int T, vptr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer: global-norm clip + AdamW on flat fp32 buffers (train_NAR.py:85-86,205).
  * ---------------------------------------------------------------------------------------------- */
 /* sumsq_dev[0] += sum(g^2) */

@@ -122,6 +122,8 @@ SIGNATURES = {
     "vptr_mse_gdl_bwd": [P, P, P, P, P, I, I, I, P],
     "vptr_nce_fwd": [P, P, P, P, I, I, I, F, P],
     "vptr_nce_bwd": [P, P, P, P, P, P, I, I, I, F, P],
+    "vptr_frame_metrics": [P, P, P, P, P, P, I, I, I, I, I, F, P],
+    "vptr_frame_metrics_accumulate": [P, P, I, I, P],
     "vptr_droppath_scales": [P, P, I, I, P, U, P],
     "vptr_sumsq": [P, L, P, P],
     "vptr_sumsq_ws": [P, L, P, P, I, P],
