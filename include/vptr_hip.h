@@ -556,6 +556,25 @@ int vptr_frame_metrics(const float* pred, const float* gt, const float* mean, co
 int vptr_frame_metrics_accumulate(const float* per_frame, double* acc, int N, int T, vptr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Clip ingest: decoded uint8 frames -> normalised fp32 model inputs (utils/dataset.py:360-438: VidCenterCrop, VidResize,
+ * VidRandomHorizontalFlip / VerticalFlip, VidToTensor, VidNormalize), bit-exact against PIL's 8-bit bilinear resize.
+ * ---------------------------------------------------------------------------------------------- */
+/* raw: uint8 [N][T][Hin][Win][C], channel-last as decoded, C in {1, 3}.  Crop box (top, left, Hc, Wc) inside the image.  Per frame
+ * and channel, on the cropped image:
+ *   1. horizontal pass to uint8, skipped when Wout == Wc:  h[y][xo] = clip8((2^21 + sum_{j < bx[xo][1]} in[y][bx[xo][0] + j] * kx[xo][j]) >> 22)
+ *   2. vertical pass over h with ky / by in the same way, skipped when Hout == Hc
+ *   3. out[c][yo'][xo'] = lut[c][v];  yo', xo' mirrored when the clip's flip bits say so (the flip follows the resize)
+ * clip8 = arithmetic shift, then clamp to 0 .. 255.  kx: int32 [Wout][ksx], bx: int32 [Wout][2] = (first column, count), both relative to
+ * the crop box; ky: [Hout][ksy], by: [Hout][2] likewise; the tables of a skipped pass may be NULL.  ksx, ksy <= 17 (a downscale of at most
+ * 8x per axis), 1 <= Hout, Wout <= 256.  lut: fp32 [C][256] (ToTensor + Normalize of every uint8 value).  flips: int32 [N] or NULL; bit 0 =
+ * horizontal, bit 1 = vertical flip of the whole clip.  Frames t < Tp go to out0 = fp32 [N][Tp][C][Hout][Wout], the others to
+ * out1 = [N][T - Tp][C][Hout][Wout]; 0 <= Tp <= T, out1 == NULL needs Tp == T (out0 == NULL needs Tp == 0).  All pointers are DEVICE
+ * pointers.  One launch; no atomics, no memset, no host sync (capturable); every limit is checked before the launch. */
+int vptr_clip_ingest(const uint8_t* raw, const int32_t* kx, const int32_t* bx, const int32_t* ky, const int32_t* by, const float* lut,
+                     const int32_t* flips, float* out0, float* out1, int N, int T, int Tp, int Hin, int Win, int C, int top, int left,
+                     int Hc, int Wc, int Hout, int Wout, int ksx, int ksy, vptr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer: global-norm clip + AdamW on flat fp32 buffers (train_NAR.py:85-86,205).
  * ---------------------------------------------------------------------------------------------- */
 /* sumsq_dev[0] += sum(g^2) */

@@ -6,7 +6,7 @@ rows = (n, t, h, w) flattened -- the reference's window partition and (T, N*HW, 
 
 Split by concern (round 6): core (configuration, seeds, raw GEMM, P16 format) / planes (weight-plane stores) / wgrad (launch planning of the
 deferred grouped weight gradients) / grads (gradient destinations: slabs, arena, autograd hand-off) / linear / norm / attention / convffn /
-layout / conv / losses / metrics (operator wrappers).  `vptr_amd.ops.<name>` keeps resolving every name the single module had.
+layout / conv / losses / metrics / ingest (operator wrappers).  `vptr_amd.ops.<name>` keeps resolving every name the single module had.
 """
 from .core import (  # noqa: F401
     ACT_NONE, ACT_GELU, ACT_RELU, ACT_LRELU, PAD_MODES, _Config, config, set_deterministic, _direct_apply, _seed_state, _seed_scope,
@@ -59,5 +59,8 @@ from .losses import (  # noqa: F401
 from .metrics import (  # noqa: F401
     FRAME_METRICS_BAND, FRAME_METRICS_MAX_W, frame_metrics,
 )
-from . import core, planes, wgrad, grads, linear, norm, attention, convffn, layout, conv, losses, metrics  # noqa: F401,E402
+from .ingest import (  # noqa: F401
+    INGEST_MAX_OUT, INGEST_MAX_KSIZE, ingest_clips,
+)
+from . import core, planes, wgrad, grads, linear, norm, attention, convffn, layout, conv, losses, metrics, ingest  # noqa: F401,E402
 from .._lib import lib  # noqa: F401,E402  (tools patch ops.lib entry points)
