@@ -275,3 +275,147 @@ def norm_act_ln_inputs(case):
     w, b = fill.rand_normal((HW, Fc), seed + 2).abs() + 0.5, fill.rand_normal((HW, Fc), seed + 3, 0.3)
     rowscale = (fill.rand_input((frames,), seed + 4) > 0.2).float() / 0.8
     return x, dy, w, b, rowscale
+
+
+# ---- attention cores through the C ABI (tests/test_00b_attn_abi_gpu.py): kernel-family switch, fp64 reference builders, the plain-torch P16
+# encoder and the head-class arithmetic of the launchers; each builder is checked against an independent formulation in tests/test_cpu.py
+ATTN_MODES = ("default", "attn16", "attn16fwd", "mfma", "vector")
+
+
+class attn_kernel_mode:
+    """scope that routes every attention geometry to one kernel family (the launchers read the variables per call): "default" (problems of at
+    most 16 tokens on the MFMA kernels of attn16.hip -- forward without LDS, backward of the second generation when C % 4 == 0; larger ones on the
+    LDS-staged MFMA kernels of attn_mfma.hip), "attn16" = VPTR_ATTN16=2 (attn16.hip forward + its first-generation backward), "attn16fwd" =
+    VPTR_ATTN16=4 (attn16.hip forward, fp32 vector backward), "mfma" = VPTR_ATTN_MFMA=2 (attn_mfma.hip wherever it covers the geometry) and
+    "vector" = VPTR_ATTN_MFMA=0 (the fp32 vector kernels of attn.hip everywhere); the variables' earlier values come back on exit"""
+
+    def __init__(self, mode):
+        assert mode in ATTN_MODES, mode
+        self.mode = mode
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in ("VPTR_ATTN_MFMA", "VPTR_ATTN16")}
+        os.environ.pop("VPTR_ATTN16", None)
+        if self.mode in ("default", "attn16", "attn16fwd"):
+            os.environ.pop("VPTR_ATTN_MFMA", None)
+            if self.mode != "default":
+                os.environ["VPTR_ATTN16"] = "2" if self.mode == "attn16" else "4"
+        else:
+            os.environ["VPTR_ATTN_MFMA"] = "2" if self.mode == "mfma" else "0"
+        return self.mode
+
+    def __exit__(self, *exc):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        return False
+
+
+def current_attn_mode():
+    """name of the kernel-family routing the environment selects right now (the inverse of attn_kernel_mode)"""
+    m, e = os.environ.get("VPTR_ATTN_MFMA"), os.environ.get("VPTR_ATTN16")
+    if m is not None and int(m) != 1:
+        return "mfma" if int(m) == 2 else "vector"
+    return {None: "default", "1": "default", "2": "attn16", "4": "attn16fwd"}.get(e, "VPTR_ATTN16=%s" % e)
+
+
+# (N, Tq, Tk, H, W, ws, C, nh) of the TSLMA core tests: the K64 model's own geometry (head dim 66: 115 KB of dynamic LDS in the backward, 7 key
+# groups that leave 50 of the 512 threads without dK / dV ownership, 23 of the 24 accumulators, clamped duplicate keys in the last group); a cross
+# case with Tq != Tk on a non-square map with 2 x 3 windows per frame (head dim 6); Lq = 20 (not a multiple of the 16-query chunk); Lq = 12 < 16 at
+# head dim 16; 6 heads of 8; Lk = 168 = TS_NACC * (512 / 66), the backward's key limit
+TS_GEOMS = [(1, 10, 10, 8, 8, 4, 528, 8), (2, 3, 7, 4, 6, 2, 48, 8), (1, 5, 5, 4, 4, 2, 48, 8), (1, 3, 4, 6, 4, 2, 128, 8), (2, 2, 3, 4, 8, 4, 48, 6),
+            (1, 2, 42, 2, 2, 2, 528, 8)]
+
+
+def _attn_fwd(ins, gather, scatter, nh, bias=None, causal=False, mask=None):
+    """differentiable fp64 forward: ins = (q, k, v[, table]); gather(t, which) -> [problems, L, C] (which: 0 query side, 1 key side), scatter its
+    inverse for the query side; bias: callable on the table -> [nh, Lq, Lk]; mask [problems, nh, Lq, Lk] multiplies the probabilities"""
+    from oracle import vptr_oracle as O
+    qw, kw, vw = gather(ins[0], 0), gather(ins[1], 1), gather(ins[2], 1)
+    b = bias(ins[3]) if bias is not None else None
+    if mask is None:
+        return scatter(O._attend(O._heads(qw, nh), O._heads(kw, nh), O._heads(vw, nh), b, causal))
+    with O.dropout_masks({"core.probs": mask.double()}):
+        return scatter(O._attend(O._heads(qw, nh), O._heads(kw, nh), O._heads(vw, nh), b, causal, drop_site="core.probs"))
+
+
+def _attn_ref(ins, gather, scatter, go, nh, bias=None, causal=False, mask=None, dq_scale=1.0):
+    """o = _attn_fwd(...) and the gradients of the leaves under the upstream gradient go, dq multiplied by dq_scale"""
+    o = _attn_fwd(ins, gather, scatter, nh, bias, causal, mask)
+    (o * go.double()).sum().backward()
+    out = {"o": o.detach(), "dq": ins[0].grad * dq_scale, "dk": ins[1].grad, "dv": ins[2].grad}
+    if bias is not None:
+        out["dtable"] = ins[3].grad
+    return out
+
+
+def _win_maps(B, H, W, C, nh, ws, rel_index):
+    from oracle import vptr_oracle as O
+    L = ws * ws
+    return (lambda t, _: O.win_partition(t.reshape(B, H, W, C), ws), lambda o: O.win_reverse(o, B, H, W, ws).reshape(B * H * W, C),
+            None if rel_index is None else (lambda t: t[rel_index.reshape(-1)].reshape(L, L, nh).permute(2, 0, 1)))
+
+
+def win_attn_fwd64(q, k, v, table, B, H, W, nh, ws, rel_index=None, mask=None):
+    """the differentiable fp64 forward behind win_attn_ref (torch.autograd.gradcheck runs on it in tests/test_cpu.py)"""
+    gather, scatter, bias = _win_maps(B, H, W, q.shape[1], nh, ws, rel_index if table is not None else None)
+    return _attn_fwd((q, k, v) if table is None else (q, k, v, table), gather, scatter, nh, bias, False, mask)
+
+
+def win_attn_ref(q, k, v, go, B, H, W, nh, ws, table=None, rel_index=None, mask=None, dq_scale=1.0):
+    """fp64 local-window attention of vptr_winattn_fwd / _bwd: q (pre-scaled), k, v, go [B*H*W, C] token-major, table [(2ws-1)^2, nh] with
+    rel_index [L, L] or None, mask [windows, nh, L, L] (0 or 1 / keep; windows in (b, wy, wx) order) or None.  Returns fp64 o, dq (the plain
+    gradient times dq_scale), dk, dv [B*H*W, C] and, with a table, dtable."""
+    ins = [t.double().clone().requires_grad_(True) for t in ((q, k, v) if table is None else (q, k, v, table))]
+    gather, scatter, bias = _win_maps(B, H, W, q.shape[1], nh, ws, rel_index if table is not None else None)
+    return _attn_ref(ins, gather, scatter, go, nh, bias, False, mask, dq_scale)
+
+
+def temporal_attn_ref(q, k, v, go, N, Tq, Tk, HW, nh, causal=False, mask=None, dq_scale=1.0):
+    """fp64 per-pixel temporal attention of vptr_tattn_fwd / _bwd: q, go [(n, tq, p), C], k, v [(n, tk, p), C]; mask [N * HW, nh, Tq, Tk] with the
+    problems in (n, pixel) order"""
+    C = q.shape[1]
+
+    def seq(t, which):
+        T = Tk if which else Tq
+        return t.reshape(N, T, HW, C).permute(0, 2, 1, 3).reshape(N * HW, T, C)
+    ins = [t.double().clone().requires_grad_(True) for t in (q, k, v)]
+    return _attn_ref(ins, seq, lambda o: o.reshape(N, HW, Tq, C).permute(0, 2, 1, 3).reshape(N * Tq * HW, C), go, nh, None, causal, mask, dq_scale)
+
+
+def ts_attn_ref(q, k, v, go, N, Tq, Tk, H, W, ws, nh, mask=None):
+    """fp64 temporal-spatial window attention of vptr_tsattn_fwd / _bwd from the explicit gather by window (ts_gather); mask [windows, nh, Lq, Lk]"""
+    ins = [t.double().clone().requires_grad_(True) for t in (q, k, v)]
+    return _attn_ref(ins, lambda t, which: ts_gather(t, N, Tk if which else Tq, H, W, ws), lambda o: ts_scatter(o, N, Tq, H, W, ws), go, nh, None,
+                     False, mask, 1.0)
+
+
+def p16_encode(x):
+    """fp32 [rows, C] (C % 16 == 0) -> the P16 tensor of the same shape and dtype with plain torch ops: per 16-channel granule 16 bf16 hi
+    (round to nearest even of x) followed by 16 bf16 lo = bf16(x - hi); the inverse of ops.core.p16_decode up to 2^-17 relative per element"""
+    C = x.shape[-1]
+    assert C % 16 == 0 and x.dtype == torch.float32
+    g = x.contiguous().reshape(-1, C // 16, 16)
+    hi = g.to(torch.bfloat16)
+    lo = (g - hi.float()).to(torch.bfloat16)
+    return torch.stack([hi, lo], 2).reshape(-1).view(torch.float32).reshape(x.shape)
+
+
+def attn_head_classes(hd, C_mod4_zero=True):
+    """(plain, second-generation) instantiation classes (nb32, nb16) of an even head dim: the first-generation attn16 kernels and attn_mfma choose
+    by (ceil(hd / 32), ceil(hd / 16)); the second-generation attn16 kernels by the same of the head's SPAN, hd + 2 when hd % 4 != 0 (a head
+    that starts on an odd channel pair begins 2 channels early).  The launchers' if-chains map the pair onto the compiled instantiation."""
+    def inst(n32, n16, gen2):
+        if n32 == 1:
+            return (1, 1) if n16 == 1 else (1, 2)
+        if n32 == 2:
+            return (2, 3) if n16 == 3 else (2, 4)
+        if n16 == 5:
+            return (3, 5)
+        if n32 == 3 or not gen2:
+            return (3, 6)
+        return (4, 7)
+    span = hd + (2 if hd % 4 else 0)
+    return inst(-(-hd // 32), -(-hd // 16), False), inst(-(-span // 32), -(-span // 16), True)

@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import rel
+from helpers import TS_GEOMS, attn_kernel_mode, rel
 from oracle import fill
 from oracle import vptr_oracle as O
 
@@ -308,25 +308,8 @@ def attn_mode(request):
     attn_mfma.hip), VPTR_ATTN16=2 (attn16.hip forward + its first-generation backward), VPTR_ATTN16=4 (attn16.hip forward, fp32 vector
     backward), VPTR_ATTN_MFMA=2 (attn_mfma.hip wherever it covers the geometry) and VPTR_ATTN_MFMA=0 (the fp32 vector kernels of
     attn.hip everywhere)"""
-    import os
-    old = os.environ.get("VPTR_ATTN_MFMA")
-    old16 = os.environ.get("VPTR_ATTN16")
-    os.environ.pop("VPTR_ATTN16", None)
-    if request.param in ("default", "attn16", "attn16fwd"):
-        os.environ.pop("VPTR_ATTN_MFMA", None)
-        if request.param != "default":
-            os.environ["VPTR_ATTN16"] = "2" if request.param == "attn16" else "4"
-    else:
-        os.environ["VPTR_ATTN_MFMA"] = "2" if request.param == "mfma" else "0"
-    yield request.param
-    if old16 is None:
-        os.environ.pop("VPTR_ATTN16", None)
-    else:
-        os.environ["VPTR_ATTN16"] = old16
-    if old is None:
-        os.environ.pop("VPTR_ATTN_MFMA", None)
-    else:
-        os.environ["VPTR_ATTN_MFMA"] = old
+    with attn_kernel_mode(request.param) as mode:
+        yield mode
 
 
 @pytest.mark.parametrize("ws,H,W,C", [(4, 8, 8, 48), (8, 16, 8, 48), (4, 8, 8, 528), (8, 16, 16, 528), (2, 4, 6, 64)])
@@ -419,14 +402,6 @@ def test_attention_partial_head_groups(ops, dev, nh, C):
     assert rel(od, o) < TOLA
     for a, c in zip(ds, ins):
         assert rel(a.grad, c.grad) < 1e-4
-
-
-# (N, Tq, Tk, H, W, ws, C, nh): the K64 model's own geometry (head dim 66: 115 KB of dynamic LDS in the backward, 7 key groups that leave 50 of
-# the 512 threads without dK / dV ownership, 23 of the 24 accumulators, clamped duplicate keys in the last group); a cross case with Tq != Tk on
-# a non-square map with 2 x 3 windows per frame (head dim 6); Lq = 20 (not a multiple of the 16-query chunk); Lq = 12 < 16 at head dim 16;
-# 6 heads of 8; Lk = 168 = TS_NACC * (512 / 66), the backward's key limit
-TS_GEOMS = [(1, 10, 10, 8, 8, 4, 528, 8), (2, 3, 7, 4, 6, 2, 48, 8), (1, 5, 5, 4, 4, 2, 48, 8), (1, 3, 4, 6, 4, 2, 128, 8), (2, 2, 3, 4, 8, 4, 48, 6),
-            (1, 2, 42, 2, 2, 2, 528, 8)]
 
 
 def _ts_reference(q, k, v, go, N, Tq, Tk, H, W, ws, nh, mask=None):

@@ -810,3 +810,193 @@ def test_deferred_bwd_cases_input_conditions():
         share = float((pre.abs() < KINK * pre.pow(2).mean().sqrt()).double().mean())
         assert share <= KINK_CAP, (case, share)
         assert 0 < int((rs == 0).sum()) < frames, case
+
+
+# ---- the attention cores through the C ABI (tests/test_00b_attn_abi_gpu.py): reference builders, P16 encoder, head classes, emulated cases ---------
+def _sdpa_heads(t, nh):
+    P, L, C = t.shape
+    return t.reshape(P, L, nh, C // nh).transpose(1, 2)
+
+
+@pytest.mark.parametrize("with_table", [True, False])
+def test_win_attn_ref_matches_sdpa(with_table):
+    """helpers.win_attn_ref (O.win_partition + O._heads + O._attend) == F.scaled_dot_product_attention in fp64 with scale = 1 and the bias as an
+    additive mask, on windows gathered by explicit row indices (helpers.ts_rows with T = 1), non-square map, several windows per frame;
+    gradients by autograd of that formulation, dq times dq_scale"""
+    import torch.nn.functional as F
+    from helpers import ts_rows, win_attn_ref
+    B, H, W, ws, nh, C = 2, 4, 6, 2, 3, 12
+    L, n, sc = ws * ws, B * H * W, 0.37
+    q, k, v, go = (fill.rand_normal((n, C), 40 + i, 0.5 if i < 2 else 1.0) for i in range(4))
+    table, idx = (fill.rand_normal(((2 * ws - 1) ** 2, nh), 44, 0.5), O.rpe_index(ws)) if with_table else (None, None)
+    ref = win_attn_ref(q, k, v, go, B, H, W, nh, ws, table, idx, None, sc)
+    rows = ts_rows(B, 1, H, W, ws).reshape(-1)
+    ins = [t.double().requires_grad_(True) for t in ((q, k, v, table) if with_table else (q, k, v))]
+    g = [_sdpa_heads(t[rows].reshape(-1, L, C), nh) for t in ins[:3]]
+    bias = ins[3][idx.reshape(-1)].reshape(L, L, nh).permute(2, 0, 1) if with_table else None
+    o = F.scaled_dot_product_attention(g[0], g[1], g[2], attn_mask=bias, scale=1.0).transpose(1, 2).reshape(-1, C)
+    full = torch.zeros(n, C, dtype=torch.float64).index_add(0, rows, o)
+    grads = torch.autograd.grad((full * go.double()).sum(), ins)
+    assert rel(ref["o"], full) < 1e-13
+    assert rel(ref["dq"], grads[0] * sc) < 1e-12 and rel(ref["dk"], grads[1]) < 1e-12 and rel(ref["dv"], grads[2]) < 1e-12
+    if with_table:
+        assert rel(ref["dtable"], grads[3]) < 1e-12
+
+
+@pytest.mark.parametrize("Tq,Tk,causal", [(5, 5, True), (3, 7, False)])
+def test_temporal_attn_ref_matches_sdpa(Tq, Tk, causal):
+    """helpers.temporal_attn_ref == F.scaled_dot_product_attention (fp64, scale = 1, causal as an additive -inf mask) per (n, pixel) sequence
+    gathered by explicit row arithmetic (row = (n * T + t) * HW + pixel)"""
+    import torch.nn.functional as F
+    from helpers import temporal_attn_ref
+    N, HW, nh, C, sc = 2, 3, 2, 8, 0.5
+    q, go = fill.rand_normal((N * Tq * HW, C), 50, 0.5), fill.rand_normal((N * Tq * HW, C), 53)
+    k, v = fill.rand_normal((N * Tk * HW, C), 51, 0.5), fill.rand_normal((N * Tk * HW, C), 52)
+    ref = temporal_attn_ref(q, k, v, go, N, Tq, Tk, HW, nh, causal, None, sc)
+
+    def rows(T):
+        n, p, t = torch.meshgrid(torch.arange(N), torch.arange(HW), torch.arange(T), indexing="ij")
+        return ((n * T + t) * HW + p).reshape(-1)
+    ins = [t.double().requires_grad_(True) for t in (q, k, v)]
+    g = [_sdpa_heads(t[rows(T)].reshape(N * HW, T, C), nh) for t, T in zip(ins, (Tq, Tk, Tk))]
+    am = torch.zeros(Tq, Tk, dtype=torch.float64).masked_fill(torch.arange(Tk)[None, :] > torch.arange(Tq)[:, None], float("-inf")) if causal else None
+    o = F.scaled_dot_product_attention(g[0], g[1], g[2], attn_mask=am, scale=1.0).transpose(1, 2).reshape(-1, C)
+    full = torch.zeros(N * Tq * HW, C, dtype=torch.float64).index_add(0, rows(Tq), o)
+    grads = torch.autograd.grad((full * go.double()).sum(), ins)
+    assert rel(ref["o"], full) < 1e-13
+    assert rel(ref["dq"], grads[0] * sc) < 1e-12 and rel(ref["dk"], grads[1]) < 1e-12 and rel(ref["dv"], grads[2]) < 1e-12
+
+
+def test_win_attn_ref_gradients_gradcheck():
+    """the differentiable forward behind helpers.win_attn_ref on 2 windows of head dim 4 with a bias table and a dropout mask: analytic vs
+    numerical Jacobians (torch.autograd.gradcheck, fp64), and win_attn_ref's gradients == autograd.grad of that forward"""
+    from helpers import win_attn_fwd64, win_attn_ref
+    B, H, W, ws, nh, C = 1, 2, 4, 2, 2, 8
+    n = B * H * W
+    q, k, v, go = (fill.rand_normal((n, C), 60 + i, 0.5 if i < 2 else 1.0) for i in range(4))
+    table, idx = fill.rand_normal((9, nh), 64, 0.5), O.rpe_index(ws)
+    mask = (fill.rand_input((2, nh, 4, 4), 65) >= 0.2).double() / 0.8
+    ins = [t.double().requires_grad_(True) for t in (q, k, v, table)]
+    assert torch.autograd.gradcheck(lambda a, b, c, d: win_attn_fwd64(a, b, c, d, B, H, W, nh, ws, idx, mask), ins, eps=1e-6, atol=1e-7, rtol=1e-5)
+    grads = torch.autograd.grad((win_attn_fwd64(*ins, B, H, W, nh, ws, idx, mask) * go.double()).sum(), ins)
+    ref = win_attn_ref(q, k, v, go, B, H, W, nh, ws, table, idx, mask, 0.5)
+    assert rel(ref["dq"], grads[0] * 0.5) < 1e-14 and rel(ref["dk"], grads[1]) < 1e-14 and rel(ref["dv"], grads[2]) < 1e-14
+    assert rel(ref["dtable"], grads[3]) < 1e-14
+
+
+def test_p16_encode_round_trip():
+    """helpers.p16_encode (plain torch: hi = bf16(x) to nearest, lo = bf16(x - hi), 16 hi then 16 lo per granule) against the decoder: the byte
+    layout (hi plane alone = bf16(x)), and the round trip within 2^-17 relative per element on seeded data over 12 binades"""
+    from helpers import p16_encode
+    from attn_abi_cases import p16_decode
+    x = fill.rand_normal((37, 48), 70) * torch.exp2(torch.arange(-6, 6).repeat(4).float())[None, :]
+    enc = p16_encode(x)
+    assert enc.shape == x.shape and enc.dtype == torch.float32
+    planes = enc.view(torch.bfloat16).reshape(37, 3, 2, 16)
+    assert torch.equal(planes[:, :, 0].reshape(37, 48), x.to(torch.bfloat16))
+    dec = p16_decode(enc)
+    assert float(((dec.double() - x.double()).abs() / x.double().abs()).max()) <= 2.0 ** -17
+    try:
+        from vptr_amd.ops.core import p16_decode as lib_decode        # needs the built library; the restated decoder must be the same function
+    except (ImportError, OSError):
+        return
+    assert torch.equal(lib_decode(enc), dec)
+
+
+def test_attn_head_dims_cover_every_class():
+    """(nb32, nb16) of every even head dim 2 .. 98, plain (first-generation attn16, attn_mfma) and of the second-generation span: the head dims
+    of the C-ABI cases reach every instantiation that some admissible hd <= 96 reaches, in both chains; the (4, 7) branch of attn16_fwd2 /
+    attn16_bwd2 is reached by no admissible head dim (span <= 96 always: hd = 94 has span 96, hd = 96 % 4 == 0)"""
+    from attn_abi_cases import HEAD_CLASSES
+    from helpers import attn_head_classes
+    reach_plain = {attn_head_classes(hd)[0] for hd in range(2, 97, 2)}
+    reach_gen2 = {attn_head_classes(hd)[1] for hd in range(2, 97, 2)}
+    assert reach_plain == reach_gen2 == {(1, 1), (1, 2), (2, 3), (2, 4), (3, 5), (3, 6)}
+    assert (4, 7) not in reach_gen2 and attn_head_classes(98)[1] == (4, 7)        # only hd = 98 would, and attn16_ok refuses hd > 96
+    hds = [C // nh for nh, C in HEAD_CLASSES.values() if C // nh <= 96]
+    assert {attn_head_classes(hd)[0] for hd in hds} == reach_plain and {attn_head_classes(hd)[1] for hd in hds} == reach_gen2
+    assert attn_head_classes(94) == ((3, 6), (3, 6)) and attn_head_classes(66) == ((3, 5), (3, 5)) and attn_head_classes(30) == ((1, 2), (1, 2))
+    assert attn_head_classes(14) == ((1, 1), (1, 1)) and attn_head_classes(62) == ((2, 4), (2, 4)) and attn_head_classes(46) == ((2, 3), (2, 3))
+
+
+def _emu():
+    from attn_abi_cases import EmuBackend
+    return EmuBackend()
+
+
+@pytest.mark.parametrize("geom", ["win4_B3_8x8_bias", "win8_B1_8x16", "win2_B2_4x6_generic", "t5x5_causal", "t3x7", "t20x20_causal_2qblocks",
+                                  "t40x33_tileshare"])
+@pytest.mark.parametrize("hc", ["hd24_c12", "hd94_oddpair_span96"])
+def test_attn_abi_cases_against_emulation(hc, geom):
+    """the direct-call cases of tests/test_00b_attn_abi_gpu.py against a CPU emulation of the C-ABI calls (closed-form backward per head, explicit
+    row gathers, P16 outputs through helpers.p16_encode): argument order, layouts, guards, references and bars of the CASES, not the kernels"""
+    import attn_abi_cases as A
+    nh, C = A.HEAD_CLASSES[hc]
+    A.run_parity(_emu(), A.GEOMS[geom], nh, C)
+
+
+@pytest.mark.parametrize("geom", ["win4_B3_8x8_bias", "win8_B1_8x16", "t5x5_causal", "t3x7", "t20x20_causal_2qblocks"])
+def test_attn_abi_dropout_conditions_hold_for_the_oracle(geom):
+    """the dropout cases with a stand-in Bernoulli mask of the same shape: zero share in (0.08, 0.12) (the smallest mask, 3 windows x 2 heads x
+    16 x 16 = 1536 elements, puts 3 sigma at +-0.023) and a mask-free reference more than 10 x 5e-5 away -- both asserted inside run_dropout"""
+    import attn_abi_cases as A
+    assert sorted(A.DROP_GEOMS) == sorted(["win4_B3_8x8_bias", "win8_B1_8x16", "t5x5_causal", "t3x7", "t20x20_causal_2qblocks"])
+    for hc in A.DROP_HEADS:
+        nh, C = A.HEAD_CLASSES[hc]
+        A.run_dropout(_emu(), A.GEOMS[geom], nh, C)
+
+
+def test_attn_abi_contract_cases_against_emulation():
+    """table-gradient accumulation, NULL table gradient, the workspace entry point (on the 65-window geometry), TSLMA with P16 outputs, the
+    nh = 3 slot-tail cases and the argument guards, emulated"""
+    import attn_abi_cases as A
+    from helpers import TS_GEOMS
+    be = _emu()
+    for g in A.TABLE_GEOMS.values():
+        A.run_table_contract(be, g, 2, 48)
+    A.run_workspace_contract(be, A.LAUNCH_CASES["win4_65win_wpb2_tail"][0], 2, 48)
+    A.run_tslma(be, *TS_GEOMS[1])
+    for name in ("mfma_win4_15prob_4slots", "mfma_t20_15prob_2slots", "mfma_t40_9prob_1slot", "win4_65win_wpb2_tail"):
+        geom, hcs, _ = A.LAUNCH_CASES[name]
+        A.run_parity(be, geom, *hcs[0])
+
+    def raises(fn):
+        with pytest.raises(RuntimeError):
+            fn()
+    A.run_guards(be, raises)
+
+
+def test_attn_abi_case_geometries():
+    """the launch-class cases have the problem counts their ids promise (1547 = 3 mod 4 = 3 mod 8 windows above every attn16 grid, 65, 2139 =
+    3 mod 4 windows, 1551 pixels), and the <true> / <false> split of the 16-token temporal vector kernels falls between T = 11 and T = 12 at hd 66
+    (T = 10, the model's, and T = 11 take the prefetching variant, T = 16 the other)"""
+    import attn_abi_cases as A
+    P = {name: A.problem_dims(g, 0)[0] for name, (g, _, _) in A.LAUNCH_CASES.items()}
+    assert P["win4_1547win_loop_wpb8_tail"] == 1547 and 1547 % 4 == 3 and 1547 % 8 == 3 and 1547 > 3072 // 2 and 1547 > 768
+    assert P["win4_65win_wpb2_tail"] == 65 and P["win2_2139win_generic_wpb4_tail"] == 2139 and 2139 % 4 == 3 and 2139 >= 2048
+    assert P["t5_causal_1551px_4px_per_wave"] == P["t10_hd66_1551px_pf"] == P["t11_hd66_1551px_pf_limit"] == P["t16_hd66_1551px_no_pf"] == 1551
+
+    def att_pitch(hd):
+        q = (hd + 3) // 4
+        return (q + 1 if q % 2 == 0 else q) * 4
+    assert att_pitch(66) == 68 and 11 * att_pitch(66) // 2 <= 384 < 12 * att_pitch(66) // 2 and 16 * att_pitch(66) // 2 > 384
+    assert P["mfma_win4_15prob_4slots"] * 3 % 4 != 0 and P["mfma_t20_15prob_2slots"] * 3 % 2 != 0
+
+
+def test_winattn16_register_tile_covers_the_lds_tile():
+    """index arithmetic of csrc/attn.hip's rows16_load / rows16_store restated: 256 threads x 3 items stage a 16 x (pitch / 2) float2 tile, so the
+    16-token window kernels may serve a head dim only while 16 * att_pitch(hd) / 2 <= 768 (rows16_fits in the launchers): hd <= 92.  At hd 94 / 96 /
+    98 (pitch 100) row 15 would keep columns 36 .. 99 of whatever the LDS held -- the defect tests/test_00b_attn_abi_gpu.py found at hd 96"""
+    def att_pitch(hd):
+        q = (hd + 3) // 4
+        return (q + 1 if q % 2 == 0 else q) * 4
+
+    def staged(hd):            # (row, float2 column) pairs the three items of 256 threads write
+        h2 = att_pitch(hd) // 2
+        return {(e // h2, e % h2) for e in range(3 * 256) if e // h2 < 16}
+    for hd in range(2, 130, 2):
+        h2 = att_pitch(hd) // 2
+        whole = staged(hd) == {(l, d) for l in range(16) for d in range(h2)}
+        assert whole == (16 * h2 <= 768) == (hd <= 92), hd
+    missing = {(l, d) for l in range(16) for d in range(50)} - staged(96)
+    assert missing == {(15, d) for d in range(18, 50)}

@@ -118,6 +118,9 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ src, float*
 struct Rows16 {
   float2 v[3];  // items tid, tid + 256, tid + 512 of the 16 x (hp / 2) float2 tile
 };
+// the three items per thread cover a tile of at most 768 float2: pitch <= 96, i.e. head dims up to 92; wider heads (94 .. : pitch 100, the
+// last row's columns 36 .. 99 would never be staged) take the generic window kernels
+static bool rows16_fits(int hd) { return 16 * (att_pitch(hd) / 2) <= 3 * 256; }
 __device__ __forceinline__ void rows16_load(Rows16& r, const float* __restrict__ src, int win, int H, int W, int C, int nqh, int nqw,
                                             int hoff, int hd, int hp, int tid) {
   const int h2 = hp >> 1, v2 = hd >> 1;
@@ -319,7 +322,7 @@ extern "C" int vptr_winattn_fwd(const float* q, const float* k, const float* v, 
     VPTR_LAUNCH_CHECK();
     return 0;
   }
-  if (ws == 4 && hd % 2 == 0 && C % 2 == 0) {
+  if (ws == 4 && hd % 2 == 0 && C % 2 == 0 && rows16_fits(hd)) {
     const int nwin = B * (H / 4) * (W / 4);
     const int wpb = nwin >= 64 ? 2 : 1;   // two windows per workgroup: the second one's loads overlap the first one's math
     const size_t lds16 = sizeof(float) * (3 * 16 * att_pitch(hd) + 16 * 20);
@@ -474,7 +477,7 @@ extern "C" int vptr_winattn_bwd_ws(const float* q, const float* k, const float* 
     VPTR_LAUNCH_CHECK();
     return 0;
   }
-  if (ws == 4 && hd % 2 == 0 && C % 2 == 0) {
+  if (ws == 4 && hd % 2 == 0 && C % 2 == 0 && rows16_fits(hd)) {
     // many windows per workgroup: the 49 bias-table atomics per workgroup hit the same 49*nh addresses from every workgroup
     // with a bias-table gradient, fewer and longer workgroups (their 49 atomics per head all hit the same 392 words)
     const int wpb16 = nwin >= 512 ? (dbias_table ? 8 : 4) : (nwin >= 64 ? 2 : 1);
