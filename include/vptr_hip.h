@@ -575,6 +575,28 @@ int vptr_clip_ingest(const uint8_t* raw, const int32_t* kx, const int32_t* bx, c
                      int Hc, int Wc, int Hout, int Wout, int ksx, int ksy, vptr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sample panels: predicted fp32 clips -> renormalised, quantised, tiled uint8 images (utils/train_summary.py:162-198:
+ * visualize_batch_clips = append_frames, cat along W, VidReNormalize, clamp, ToPILImage; the notebook's strip of frames).
+ * ---------------------------------------------------------------------------------------------- */
+/* K in 1 .. 4 clips; clips, T, stride_n, stride_t, pad are HOST arrays of K entries.  clips[k]: DEVICE fp32 [N][T[k]][C][H][W] whose inner
+ * (C, H, W) block is contiguous, sample stride stride_n[k] and frame stride stride_t[k] in elements (>= 0: views need no copy); C in {1, 3}.
+ * a, b: DEVICE fp32 [C] or both NULL.  Per value, every operation rounded on its own (nothing contracted, no reciprocal):
+ *   z = x                       (a == NULL)        z = (x / a[c]) - b[c]      (a = fp32(1 / std), b = fp32(-mean): VidReNormalize)
+ *   clamp != 0:  z = min(max(z, 0), 1)
+ *   q = z * 255;  nearest != 0:  q = q + 0.5;   byte = trunc(q), saturating: q < 0 -> 0, q > 255 -> 255, NaN -> 0
+ * (nearest == 0 is ToPILImage's mul(255).byte(); the saturation acts only where that cast is undefined.)
+ * out: DEVICE uint8, channel-last, Cout = 3 if gray_to_rgb != 0 and C == 1 (the grey byte three times), else C; L = max T[k]:
+ *   layout 0 (frames): [N][L][H][K * W][Cout], cell (k, t) at columns k * W .. k * W + W - 1 of frame t   (torch.cat(dim=-1) as HWC)
+ *   layout 1 (sheet):  [N][K * H][L * W][Cout], clip k is a row of its L frames
+ * A cell with t >= T[k] shows frame pad[k] of clip k; pad[k] == -1: bytes of 0; -1 <= pad[k] <= T[k] - 1.
+ * 16-byte loads and dword stores when W % 4 == 0, every clips[k] is 16-byte aligned, the strides are multiples of 4 and out is 4-byte
+ * aligned; scalar accesses otherwise.  One launch; no atomics, no memset, no host sync (capturable); everything is checked before the
+ * launch. */
+int vptr_clip_panels(const float* const* clips, const int32_t* T, const int64_t* stride_n, const int64_t* stride_t, const int32_t* pad,
+                     const float* a, const float* b, uint8_t* out, int K, int N, int C, int H, int W, int clamp, int nearest,
+                     int gray_to_rgb, int layout, vptr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer: global-norm clip + AdamW on flat fp32 buffers (train_NAR.py:85-86,205).
  * ---------------------------------------------------------------------------------------------- */
 /* sumsq_dev[0] += sum(g^2) */

@@ -125,6 +125,7 @@ SIGNATURES = {
     "vptr_frame_metrics": [P, P, P, P, P, P, I, I, I, I, I, F, P],
     "vptr_frame_metrics_accumulate": [P, P, I, I, P],
     "vptr_clip_ingest": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P],
+    "vptr_clip_panels": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],   # clips, T, strides, pad: HOST arrays of K entries
     "vptr_droppath_scales": [P, P, I, I, P, U, P],
     "vptr_sumsq": [P, L, P, P],
     "vptr_sumsq_ws": [P, L, P, P, I, P],
