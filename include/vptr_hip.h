@@ -390,9 +390,13 @@ int vptr_groupstats(const float* x, float* mean, float* var, float* rstd, float 
  * per_col != 0: stats indexed by column (BN), affine [F];
  * per_col == 0: stats indexed by row / HW (LN over (F,H,W)), affine given channel-last as [HW, F].
  * rowscale (DropPath, VidHRFormer_modules.py:563-575) and residual may be null. */
-/* raw_stats != NULL (per_col == 0 only): [frames][2] per-frame sum / sum of squares of x as accumulated by its producer
- * (vptr_gemm_desc::frame_stats, vptr_dwconv3x3_fwd); the kernel derives mean / rstd from them (eps) and WRITES mean[], rstd[]
- * for the backward pass -- otherwise mean[], rstd[] are inputs. */
+/* raw_stats != NULL (per_col == 0 only; mean and rstd must not be NULL): [frames][VPTR_FRAME_STATS_STRIDE] per-frame sum / sum of squares of
+ * x as accumulated by its producer (vptr_gemm_desc::frame_stats, vptr_dwconv3x3_fwd); the kernel derives mean / rstd from them (eps) and
+ * WRITES mean[], rstd[] for the backward pass -- otherwise mean[], rstd[] are inputs.  The one-pass variance E[x^2] - mean^2 loses
+ * log2(E[x^2] / var) bits; a frame with var < 1e-2 E[x^2] (|mean| > ~10 std) gets its variance and a mean correction from a second pass over
+ * x -- but ONLY when HW * (F/4) % 256 == 0 (a workgroup then lies inside one frame) and, for the row-major kernel (fewer than 16 frames or
+ * fewer than 2^18 float4), rows * (F/4) % 256 == 0 as well.  Other geometries keep the one-pass value: relative error of the normalised
+ * output about 6e-8 * (mean / std)^2.  vptr_dwconv3x3_norm_fwd applies the same test on every geometry it accepts. */
 int vptr_norm_act_fwd(const float* x, float* mean, float* rstd, const float* w, const float* b, float* y,
                       int rows, int F, int HW, int per_col, int act, float dropout_p, const uint64_t* seed_dev,
                       uint32_t site, const float* rowscale, int rs_div, int rs_mod, const float* residual,
@@ -414,8 +418,8 @@ int vptr_norm_act_bwd_deferred(const float* dy, const float* x, const float* mea
                                float* partials, vptr_stream_t stream);
 int vptr_norm_act_bwd_partials(int rows, int F, int HW, int per_col);   /* a plain number (0: use vptr_norm_act_bwd) */
 /* depthwise 3x3, pad 1 (VidHRFormer_modules.py:404-409,433); w given tap-major [9, F]. */
-/* frame_stats (may be NULL): [frames][2] zeroed buffer that receives each frame's sum / sum of squares of y (see
- * vptr_norm_act_fwd raw_stats); needs W even and (W/2)*(F/4) % 64 == 0 */
+/* frame_stats (may be NULL): [frames][VPTR_FRAME_STATS_STRIDE] buffer (zeroed by the caller) onto which each frame's sum / sum of squares of y
+ * are ADDED at slots 0 / 1 (see vptr_norm_act_fwd raw_stats); needs W even and (W/2)*(F/4) % 64 == 0 */
 int vptr_dwconv3x3_fwd(const float* x, const float* w9, const float* b, float* y, int frames, int H, int W, int F,
                        float* frame_stats, vptr_stream_t stream);
 int vptr_dwconv3x3_bwd(const float* dy, const float* x, const float* w9, float* dx, float* dw9, float* db, int frames,
@@ -426,7 +430,8 @@ int vptr_dwconv3x3_bwd(const float* dy, const float* x, const float* w9, float* 
  * own frame_stats, as vptr_dwconv3x3_fwd); mean_out / rstd_out [frames] are written for the normalisation's backward pass
  * (vptr_norm_act_bwd*); a_half (may be NULL) receives act(norm(x)) as fp16 [frames*H*W, F] -- the only thing the backward pass needs of the
  * activated tensor is the x operand of the depthwise weight gradient, vptr_dwconv3x3_bwd_xh.  Needs W even, W / 2 dividing 16 and
- * (W/2)*(F/4) % 64 == 0; no fallback. */
+ * (W/2)*(F/4) % 64 == 0, x / y / aff_w / aff_b / w9 / b 16-byte and a_half 8-byte aligned; no fallback (a refused call returns non-zero and
+ * writes nothing). */
 int vptr_dwconv3x3_norm_fwd(const float* x, const float* raw_stats, const float* aff_w, const float* aff_b, float eps, int act,
                             const float* w9, const float* b, float* y, void* a_half, float* mean_out, float* rstd_out,
                             int frames, int H, int W, int F, float* frame_stats, vptr_stream_t stream);

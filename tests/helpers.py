@@ -419,3 +419,123 @@ def attn_head_classes(hd, C_mod4_zero=True):
         return (4, 7)
     span = hd + (2 if hd % 4 else 0)
     return inst(-(-hd // 32), -(-hd // 16), False), inst(-(-span // 32), -(-span // 16), True)
+
+
+# ---- the conv-FFN forward kernels through the C ABI (tests/test_09c_convffn_fwd_gpu.py): fp64 reference builders on channel-last rows, the
+# launchers' selection arithmetic and an fp32 emulation of the one-pass variance; each is checked in tests/test_cpu.py
+def _act64(pre, act):
+    import torch.nn.functional as F
+    return F.gelu(pre) if act == 1 else (torch.relu(pre) if act == 2 else pre)
+
+
+def norm_act_fwd_ref(x, w, b, HW, per_col, act, mask=None, keep=1.0, rowscale=None, rs_div=1, rs_mod=1, residual=None, eps=1e-5):
+    """fp64 y = rowscale[(row // rs_div) % rs_mod] * (mask / keep) * act(norm(x) * w + b) + residual of vptr_norm_act_fwd on channel-last
+    x [rows, F].  per_col: BatchNorm2d batch statistics per column (biased variance), affine [F]; otherwise LayerNorm((F,H,W)) per frame of HW
+    rows, affine [HW, F] (see norm_act_ln_bwd_ref).  mask [rows, F]: 0 / 1.  Returns y, the pre-activation and the statistics mean, rstd
+    ([F] or [frames])."""
+    rows, Fc = x.shape
+    xd = x.double()
+    if per_col:
+        mean, var = xd.mean(0), xd.var(0, unbiased=False)
+        rstd = (var + eps).rsqrt()
+        pre = (xd - mean) * rstd * w.double() + b.double()
+    else:
+        frames = rows // HW
+        assert rows == frames * HW and tuple(w.shape) == (HW, Fc)
+        xf = xd.view(frames, HW * Fc)
+        mean = xf.mean(1)
+        rstd = (xf.var(1, unbiased=False) + eps).rsqrt()
+        pre = (((xf - mean[:, None]) * rstd[:, None]).view(frames, HW, Fc) * w.double() + b.double()).reshape(rows, Fc)
+    y = _act64(pre, act)
+    if mask is not None:
+        y = y * mask.double() / keep
+    if rowscale is not None:
+        y = y * rowscale.double()[(torch.arange(rows) // rs_div) % rs_mod][:, None]
+    if residual is not None:
+        y = y + residual.double()
+    return {"y": y, "pre": pre, "mean": mean, "rstd": rstd}
+
+
+def dwconv3x3_fwd_ref(a, w9, b9, frames, H, W):
+    """fp64 depthwise 3x3 (padding 1) of channel-last a [frames * H * W, F] with the tap-major weights w9 [9, F] (tap = ky * 3 + kx) by
+    F.conv2d(groups = F); returns channel-last rows"""
+    import torch.nn.functional as F
+    Fc = a.shape[1]
+    a4 = a.double().reshape(frames, H, W, Fc).permute(0, 3, 1, 2)
+    y = F.conv2d(a4, w9.double().t().reshape(Fc, 1, 3, 3), None if b9 is None else b9.double(), padding=1, groups=Fc)
+    return y.permute(0, 2, 3, 1).reshape(frames * H * W, Fc)
+
+
+def dwconv_norm_fwd_ref(x, aw, ab, w9, b9, frames, H, W, act, eps=1e-5):
+    """fp64 reference of vptr_dwconv3x3_norm_fwd: a = act(LayerNorm((F,H,W))(x) * aw + ab) (aw, ab channel-last [H * W, F]), y = dw3x3(a) + b9.
+    Returns y, a [rows, F], the frame statistics mean, rstd [frames] and the per-frame sum / sum of squares of y (what frame_stats receives)."""
+    n = norm_act_fwd_ref(x, aw, ab, H * W, False, act, eps=eps)
+    y = dwconv3x3_fwd_ref(n["y"], w9, b9, frames, H, W)
+    yf = y.view(frames, -1)
+    return {"y": y, "a": n["y"], "mean": n["mean"], "rstd": n["rstd"], "sum": yf.sum(1), "sumsq": (yf * yf).sum(1)}
+
+
+def convffn_fwd_class(op, **g):
+    """the launch class of a conv-FFN forward call, restated from the launchers (csrc/norm_act.hip, csrc/dwconv.hip):
+    op "norm_act" (rows, F, HW, per_col, raw): kernel "col" (norm_act_fwd_kernel<true>), "row" (<false>) or "pos" (norm_act_fwd_pos_kernel), its
+        grid, the float4 count, the trips of the longest grid-stride / frame loop and whether the large-mean recompute is armed;
+    op "dwconv" (frames, H, W, F, stats): "fwd" / "fwd2" / "fwd3", or "reject";
+    op "dwconv_norm" (frames, H, W, F): "lds" / "reg" (with the slab's dynamic LDS bytes), or "reject"."""
+    cdiv = lambda a, b: (a + b - 1) // b
+    if op == "norm_act":
+        rows, Fc, HW, per_col, raw = g["rows"], g["F"], g["HW"], g["per_col"], g.get("raw", False)
+        if Fc % 4 or rows <= 0 or HW < 1 or (not per_col and rows % HW) or (raw and per_col):
+            return {"kernel": "reject"}
+        total, blocks = rows * (Fc // 4), min(cdiv(rows * (Fc // 4), 256), 8192)
+        if per_col:
+            return {"kernel": "col", "grid": (blocks, 1), "float4": total, "trips": cdiv(total, blocks * 256), "armed": False}
+        frames, P = rows // HW, HW * (Fc // 4)
+        if frames >= 16 and total >= 1 << 18:
+            gy = min(max(frames // 4, 1), 65535)
+            return {"kernel": "pos", "grid": (cdiv(P, 256), gy), "float4": total, "trips": cdiv(frames, gy), "armed": bool(raw and P % 256 == 0)}
+        return {"kernel": "row", "grid": (blocks, 1), "float4": total, "trips": cdiv(total, blocks * 256),
+                "armed": bool(raw and P % 256 == 0 and total % 256 == 0)}
+    frames, H, W, Fc = g["frames"], g["H"], g["W"], g["F"]
+    if min(frames, H, W, Fc) <= 0 or Fc % 4:
+        return {"kernel": "reject"}
+    F4, W2 = Fc // 4, W // 2
+    if op == "dwconv":
+        stats = g.get("stats", False)
+        if stats and (W % 2 or (W2 * F4) % 64):
+            return {"kernel": "reject"}
+        if W % 2 or (not stats and frames * W * F4 < 1 << 16):
+            return {"kernel": "fwd"}
+        return {"kernel": "fwd3" if 16 % W2 == 0 else "fwd2"}
+    assert op == "dwconv_norm", op
+    if W % 2 or W2 < 1 or 16 % W2 or (W2 * F4) % 64:
+        return {"kernel": "reject"}
+    if Fc % 64 == 0 and H * W <= 256 and frames <= 65535:
+        return {"kernel": "lds", "lds_bytes": H * W * 256, "grid": (Fc // 64, frames)}
+    return {"kernel": "reg", "grid": (cdiv(frames * W2 * F4, 256), 1)}
+
+
+VAR_GUARD = 1e-2      # the kernels redo the variance around the mean when var < VAR_GUARD * E[x^2]: |mean| > sqrt(1 / VAR_GUARD - 1) = 9.95 std
+
+
+def onepass_norm_emulation(x, guard, eps=1e-5):
+    """fp32 emulation of the frame normalisation from IDEAL producer sums (the fp64 sum and sum of squares of the frame rounded once to fp32):
+    mean = S / n, var = E[x^2] - mean^2 in fp32 as the four kernels compute them; when var < guard * E[x^2] the variance is redone around that
+    mean (again with ideal sums of the fp32 differences) and the mean corrected.  x: one frame (fp32, any shape).  Returns (rel-L2 of the
+    fp32 (x - mean) * rstd against fp64, recompute taken?)."""
+    f32 = np.float32
+    xv = x.detach().reshape(-1).numpy().astype(f32)
+    x64 = xv.astype(np.float64)
+    inv_n = f32(1.0) / f32(xv.size)
+    m = f32(x64.sum()) * inv_n
+    e2 = f32((x64 * x64).sum()) * inv_n
+    var = np.maximum(e2 - m * m, f32(0.0))
+    redo = bool(var < f32(guard) * e2)
+    if redo:
+        d = (xv - m).astype(np.float64)               # fp32 differences: exact inputs of the second pass
+        dm = f32(d.sum()) * inv_n
+        var = np.maximum(f32((d * d).sum()) * inv_n - dm * dm, f32(0.0))
+        m = m + dm
+    r = f32(1.0) / np.sqrt(var + f32(eps), dtype=f32)
+    got = ((xv - m) * r).astype(np.float64)
+    want = (x64 - x64.mean()) / np.sqrt(x64.var() + eps)
+    return float(np.linalg.norm(got - want) / np.linalg.norm(want)), redo

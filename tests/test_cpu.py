@@ -1000,3 +1000,172 @@ def test_winattn16_register_tile_covers_the_lds_tile():
         assert whole == (16 * h2 <= 768) == (hd <= 92), hd
     missing = {(l, d) for l in range(16) for d in range(50)} - staged(96)
     assert missing == {(15, d) for d in range(18, 50)}
+
+
+# ---- the conv-FFN forward kernels through the C ABI (tests/test_09c_convffn_fwd_gpu.py): reference builders, launch classes, the one-pass
+# variance in fp32, emulated cases -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("act", [0, 1, 2])
+def test_convffn_fwd_refs_match_the_nchw_modules(act):
+    """helpers.norm_act_fwd_ref / dwconv_norm_fwd_ref (channel-last rows, [HW, F] affine, tap-major [9, F] weights) == the modules' own NCHW
+    formulation: nn.LayerNorm((F, H, W)) or F.batch_norm on [frames, F, H, W], the activation, mask / keep, the per-row scale, the residual,
+    F.conv2d with the [F, 1, 3, 3] parameter"""
+    import torch.nn.functional as Fn
+    from helpers import dwconv_norm_fwd_ref, norm_act_fwd_ref
+    frames, H, W, Fc = 5, 2, 3, 8
+    HW, rows = H * W, frames * H * W
+    x, res = fill.rand_normal((rows, Fc), 41, 2.0) + 0.3, fill.rand_normal((rows, Fc), 42)
+    w, b = fill.rand_normal((HW, Fc), 43).abs() + 0.5, fill.rand_normal((HW, Fc), 44, 0.3)
+    mask = (fill.rand_input((rows, Fc), 45) >= 0.1).float()
+    rs, rs_div, rs_mod = torch.tensor([1.25, 0.0, 0.7]), 4, 3                # runs of 4 rows: not the frame length
+
+    def nchw(t):
+        return t.double().reshape(-1, H, W, Fc).permute(0, 3, 1, 2)
+
+    def cl(t):
+        return t.permute(0, 2, 3, 1).reshape(-1, Fc)
+
+    def actf(t):
+        return Fn.gelu(t) if act == 1 else (torch.relu(t) if act == 2 else t)
+    tail = nchw(mask) / 0.9 * nchw(rs.double()[(torch.arange(rows) // rs_div) % rs_mod][:, None].expand(rows, Fc))
+    ln = torch.nn.LayerNorm((Fc, H, W), eps=1e-5).double()
+    with torch.no_grad():
+        ln.weight.copy_(nchw(w)[0])
+        ln.bias.copy_(nchw(b)[0])
+        pre = ln(nchw(x))
+        got = norm_act_fwd_ref(x, w, b, HW, False, act, mask, 0.9, rs, rs_div, rs_mod, res)
+        assert rel(got["y"], cl(actf(pre) * tail + nchw(res))) < 1e-10 and rel(got["pre"], cl(pre)) < 1e-10
+        x4 = nchw(x)
+        assert rel(got["mean"], x4.mean((1, 2, 3))) < 1e-10 and rel(got["rstd"], (x4.var((1, 2, 3), unbiased=False) + 1e-5).rsqrt()) < 1e-10
+        # BatchNorm2d batch statistics, affine [F]
+        wc, bc = w[0], b[0]
+        pre = Fn.batch_norm(x4, None, None, wc.double(), bc.double(), True, 0.1, 1e-5)
+        got = norm_act_fwd_ref(x, wc, bc, 1, True, act, mask, 0.9, rs, rs_div, rs_mod, res)
+        assert rel(got["y"], cl(actf(pre) * tail + nchw(res))) < 1e-10
+        assert rel(got["mean"], x4.mean((0, 2, 3))) < 1e-10 and rel(got["rstd"], (x4.var((0, 2, 3), unbiased=False) + 1e-5).rsqrt()) < 1e-10
+        # the fused operator
+        wt, b9 = fill.rand_normal((Fc, 1, 3, 3), 46, 0.3), fill.rand_normal((Fc,), 47, 0.3)
+        a = actf(ln(x4))
+        y = Fn.conv2d(a, wt.double(), b9.double(), padding=1, groups=Fc)
+        got = dwconv_norm_fwd_ref(x, w, b, wt.reshape(Fc, 9).t().contiguous(), b9, frames, H, W, act)
+        assert rel(got["y"], cl(y)) < 1e-10 and rel(got["a"], cl(a)) < 1e-10
+        assert rel(got["sum"], y.sum((1, 2, 3))) < 1e-10 and rel(got["sumsq"], (y * y).sum((1, 2, 3))) < 1e-10
+        assert rel(got["mean"], x4.mean((1, 2, 3))) < 1e-10
+
+
+def test_convffn_fwd_cases_land_in_their_launch_classes():
+    """the launchers' selection arithmetic restated (helpers.convffn_fwd_class): every geometry of tests/convffn_fwd_cases.py reaches the kernel,
+    the grid, the trip count and the armed / not-armed state of the large-mean recompute that its row claims"""
+    import convffn_fwd_cases as C
+    from helpers import convffn_fwd_class
+    for gid, (per_col, rows, HW, Fc) in C.NA_GEOMS.items():
+        kernel, grid, n4, trips, armed = C.NA_CLASSES[gid]
+        for raw in ((False,) if per_col else (False, True)):
+            cls = convffn_fwd_class("norm_act", rows=rows, F=Fc, HW=HW, per_col=per_col, raw=raw)
+            assert (cls["kernel"], cls["grid"], cls["float4"], cls["trips"], cls["armed"]) == (kernel, grid, n4, trips, armed and raw), (gid, cls)
+    assert 615 % 256 != 0 and 2099200 - 8192 * 256 == 2048                       # a partial last workgroup; what the second trip covers
+    assert 12 * 20 // 4 == 60 and 256 % 60 != 0                                  # ln_small: workgroups straddle frames
+    assert 15 * 64 * 256 < 1 << 18 == 16 * 64 * 256                              # one frame short of / exactly at the switch
+    assert 15000 - 58 * 256 == 152 and 18 > 4 * 4                                # ln_pos_ragged: live threads of the last x-workgroup; a fifth trip
+    assert convffn_fwd_class("norm_act", rows=24, F=20, HW=4, per_col=True, raw=True)["kernel"] == "reject"
+    assert {v for g in C.NA_GEOMS for g2, v in C.na_cases() if g2 == g} == {"plain", "full", "raw", "p16", "relu"}
+    assert ("bn_small", "p16") not in C.na_cases() and ("ln_small", "p16") not in C.na_cases() and ("bn_stride", "raw") not in C.na_cases()
+    for place, (kind, frames, H, W, Fc) in C.GUARD_PLACES.items():
+        if kind == "na":
+            cls = convffn_fwd_class("norm_act", rows=frames * H * W, F=Fc, HW=H * W, per_col=False, raw=True)
+            assert cls["armed"] and cls["kernel"] == {"ln_armed": "row", "ln_pos_min": "pos"}[place]
+        else:
+            assert convffn_fwd_class("dwconv_norm", frames=frames, H=H, W=W, F=Fc)["kernel"] == place[4:]
+    for geom, kernel in C.DW_STATS_GEOMS.items():
+        assert convffn_fwd_class("dwconv", frames=geom[0], H=geom[1], W=geom[2], F=geom[3], stats=True)["kernel"] == kernel, geom
+    for geom in C.DW_STATS_REJECTS:
+        assert convffn_fwd_class("dwconv", frames=geom[0], H=geom[1], W=geom[2], F=geom[3], stats=True)["kernel"] == "reject", geom
+    for geom, kernel in C.DWN_GEOMS.items():
+        assert convffn_fwd_class("dwconv_norm", frames=geom[0], H=geom[1], W=geom[2], F=geom[3])["kernel"] == kernel, geom
+    for geom in C.DWN_REJECTS.values():
+        assert convffn_fwd_class("dwconv_norm", frames=geom[0], H=geom[1], W=geom[2], F=geom[3])["kernel"] == "reject", geom
+    assert convffn_fwd_class("dwconv_norm", frames=2, H=16, W=16, F=64)["lds_bytes"] == 64 * 1024
+    for frames, H, W, Fc in C.CHAIN_GEOMS:
+        assert convffn_fwd_class("dwconv", frames=frames, H=H, W=W, F=Fc, stats=True)["kernel"] == "fwd3"
+
+
+def test_onepass_variance_guard_threshold():
+    """fp32 emulation of E[x^2] - mean^2 from ideal sums on a 64 x 1024 frame x = r + N(0, 1), 12 seeds: below the guard (var < VAR_GUARD E[x^2],
+    |mean| > 9.95 std) the cancellation costs about eps32 (mean / std)^2 and stays at or under half the fp32 vector bar; with the recompute
+    it does so up to ratio 100.  Under the former guard of 1e-3 (31.6 std) ratio 25 took the one-pass branch and missed the bar itself"""
+    from helpers import VAR_GUARD, onepass_norm_emulation
+    TOLV = 2e-5
+
+    def worst(r, guard):
+        vals = [onepass_norm_emulation(fill.rand_normal((64, 1024), 9100 + s) + float(r), guard) for s in range(12)]
+        assert len({redo for _, redo in vals}) == 1, r
+        return max(v for v, _ in vals), vals[0][1]
+    assert VAR_GUARD == 1e-2 and (1.0 / VAR_GUARD - 1.0) ** 0.5 < 10.0
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vptr_amd", "csrc")
+    tests_in = {f: len(re.findall(r"var < ([0-9.e-]+)f \* e2", open(os.path.join(csrc, f)).read())) for f in ("norm_act.hip", "dwconv.hip")}
+    lits = {m for f in tests_in for m in re.findall(r"var < ([0-9.e-]+)f \* e2", open(os.path.join(csrc, f)).read())}
+    assert tests_in == {"norm_act.hip": 2, "dwconv.hip": 2} and lits == {"1e-2"}, (tests_in, lits)      # the four copies hold the same guard
+    for r in (1.0, 5.0, 9.5, 9.8):
+        v, redo = worst(r, VAR_GUARD)
+        assert not redo and v <= TOLV / 2, (r, v)
+    for r in (10.2, 12.0, 25.0, 31.0, 100.0):
+        v, redo = worst(r, VAR_GUARD)
+        assert redo and v <= TOLV / 2, (r, v)
+    v, redo = worst(25.0, 1e-3)
+    assert not redo and v > TOLV, v
+
+
+@pytest.mark.parametrize("part", ["norm_act", "guard", "dwconv_stats", "dwconv_norm", "chain"])
+def test_convffn_fwd_cases_against_emulation(part, capsys):
+    """the direct-call cases of tests/test_09c_convffn_fwd_gpu.py against a CPU emulation of the three entry points written from the header:
+    argument order, layouts, guards, statistics rows, references and bars of the CASES, not the kernels (the three largest norm_act geometries
+    are left to the GPU run)"""
+    import convffn_fwd_cases as C
+    be = C.EmuBackend()
+    if part == "norm_act":
+        for gid, variant in C.na_cases():
+            if gid in ("bn_small", "ln_small", "ln_armed", "ln_pos_ragged"):
+                C.run_norm_act(be, gid, variant)
+        C.run_norm_act_rejects(be)
+    elif part == "guard":
+        for place in ("ln_armed", "dwn_lds", "dwn_reg"):
+            for r in (9, 25):
+                C.run_guard(be, place, r)
+    elif part == "dwconv_stats":
+        for geom in C.DW_STATS_GEOMS:
+            C.run_dwconv_stats(be, geom)
+        C.run_dwconv_stats_rejects(be)
+    elif part == "dwconv_norm":
+        for geom, variant in C.dwn_cases():
+            C.run_dwn(be, geom, variant)
+        for geom, variant in C.dwn_cases(True):
+            C.run_dwn_half_elements(be, geom, variant)
+        C.run_dwn_rejects(be)
+    else:
+        C.run_chain(be, C.CHAIN_GEOMS[0])
+
+
+def test_gelu_polynomial_leaves_room_for_the_fp16_rounding():
+    """vptr_phi's erfc polynomial (coefficients read from csrc/common.h) replayed in fp32 on x in [-10, 0]: the error of x * Phi(x) stays inside
+    2^-22 |ref| + 2^-24, what the round-to-nearest bound of the fp16 side copy (2^-11 |ref| + 2^-24) leaves an fp32 value that sits next to a
+    power of two; Abramowitz-Stegun's five coefficients (1.5e-7 absolute) exceed it 3.5 times near x = -3.7"""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vptr_amd", "csrc", "common.h")).read()
+    body = src[src.index("const float poly = t * ("):src.index("const float h = 0.5f * poly * e;")]
+    coef = [float(c) for c in re.findall(r"(-?[0-9]+\.[0-9]+)f", body)]
+    p = float(re.search(r"1\.0f \+ ([0-9.]+)f \* ax", src).group(1))
+    assert len(coef) == 9 and p == 0.3275911
+    f32 = np.float32
+    x = -np.linspace(0.0, 10.0, 400001).astype(f32)
+    x64 = x.astype(np.float64)
+    ref = x64 * 0.5 * torch.special.erfc(torch.from_numpy(-x64) / 2 ** 0.5).numpy()
+
+    def worst(cs):
+        ax = np.abs(x) * f32(0.70710678118654752)
+        t = (f32(1) / (f32(1) + f32(p) * ax)).astype(f32)
+        e = np.exp(-(ax * ax).astype(f32)).astype(f32)
+        poly = np.full_like(t, f32(cs[-1]))
+        for c in cs[-2::-1]:
+            poly = (poly * t + f32(c)).astype(f32)
+        got = (x * (f32(0.5) * (poly * t).astype(f32) * e).astype(f32)).astype(np.float64)
+        return float((np.abs(got - ref) / (2.0 ** -22 * np.abs(ref) + 2.0 ** -24)).max())
+    assert worst(coef) <= 1.0, worst(coef)
+    assert worst([0.254829592, -0.284496736, 1.421413741, -1.453152027, 1.061405429]) > 3.0

@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void dwconv_norm_fwd3_kernel(const float* __re
   float m = raw_stats[VPTR_FRAME_STATS_STRIDE * f] * inv_n;
   const float e2 = raw_stats[VPTR_FRAME_STATS_STRIDE * f + 1] * inv_n;
   float var = fmaxf(e2 - m * m, 0.f);
-  if (var < 1e-3f * e2) {   // wave-uniform (f is): |mean| > ~30 std -- exact second pass of this wave over its frame, around the approximate mean
+  if (var < 1e-2f * e2) {   // wave-uniform (f is): |mean| > ~10 std -- exact second pass of this wave over its frame, around the approximate mean
     const float4* xf = x + f * P;
     float sq = 0.f, s1 = 0.f;
     for (int j = threadIdx.x & 63; j < P; j += 64) {
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256) void dwconv_norm_lds_kernel(const float* __res
   float m = raw_stats[VPTR_FRAME_STATS_STRIDE * f] * inv_n;
   const float e2 = raw_stats[VPTR_FRAME_STATS_STRIDE * f + 1] * inv_n;
   float var = fmaxf(e2 - m * m, 0.f);
-  if (var < 1e-3f * e2) {   // block-uniform: |mean| > ~30 std -- exact second pass of every wave over its frame, around the approximate mean
+  if (var < 1e-2f * e2) {   // block-uniform: |mean| > ~10 std -- exact second pass of every wave over its frame, around the approximate mean
     const float4* xf = x + f * P;
     float sq = 0.f, s1 = 0.f;
     for (int j = tid & 63; j < P; j += 64) {

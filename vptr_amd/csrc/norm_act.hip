@@ -174,10 +174,13 @@ __global__ __launch_bounds__(256) void norm_act_fwd_kernel(const float* __restri
         m = raw_stats[VPTR_FRAME_STATS_STRIDE * f] * inv_n;
         const float e2 = raw_stats[VPTR_FRAME_STATS_STRIDE * f + 1] * inv_n;
         float var = fmaxf(e2 - m * m, 0.f);
-        // E[x^2] - mean^2 from fp32 sums loses log2(E[x^2] / var) bits.  |mean| > ~30 std: recompute the frame's variance around its
-        // mean (exact two-pass; this workgroup reads the whole frame -- every workgroup of the frame finds the same value).  guard:
-        // a workgroup iteration lies inside ONE frame (HW * F4 % 256 == 0, checked by the launcher), so the branch is uniform.
-        if (guard && var < 1e-3f * e2) {
+        // E[x^2] - mean^2 from fp32 sums loses log2(E[x^2] / var) bits: the normalised output is off by about eps32 * (mean / std)^2,
+        // 5.6e-6 at |mean| = 9.5 std and past the 2e-5 bar of the fp32 vector kernels from ~18 std on (tests/test_cpu.py emulates it).
+        // var < 1e-2 E[x^2], i.e. |mean| > ~10 std: recompute the frame's variance around its mean (exact two-pass; this workgroup
+        // reads the whole frame -- every workgroup of the frame finds the same value).  guard: a workgroup iteration lies inside ONE
+        // frame (HW * F4 % 256 == 0, checked by the launcher), so the branch is uniform.  The same test in norm_act_fwd_pos_kernel,
+        // dwconv_norm_fwd3_kernel and dwconv_norm_lds_kernel (dwconv.hip): keep the four identical.
+        if (guard && var < 1e-2f * e2) {
           const float4* xf = reinterpret_cast<const float4*>(x) + (int64_t)f * HW * F4;
           float sq = 0.f, s1 = 0.f;   // around the approximate mean m: both sums are small, nothing cancels
           for (int j = threadIdx.x; j < HW * F4; j += 256) {
@@ -254,7 +257,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_pos_kernel(const float* __re
       m = raw_stats[VPTR_FRAME_STATS_STRIDE * f] * inv_n;
       const float e2 = raw_stats[VPTR_FRAME_STATS_STRIDE * f + 1] * inv_n;
       float var = fmaxf(e2 - m * m, 0.f);
-      if (guard && var < 1e-3f * e2) {   // see norm_act_fwd_kernel; guard implies P % 256 == 0: every thread of the workgroup is live
+      if (guard && var < 1e-2f * e2) {   // see norm_act_fwd_kernel; guard implies P % 256 == 0: every thread of the workgroup is live
         const float4* xf = reinterpret_cast<const float4*>(x) + (int64_t)f * P;
         float sq = 0.f, s1 = 0.f;
         for (int j = threadIdx.x; j < P; j += 256) {
