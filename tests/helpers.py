@@ -539,3 +539,210 @@ def onepass_norm_emulation(x, guard, eps=1e-5):
     got = ((xv - m) * r).astype(np.float64)
     want = (x64 - x64.mean()) / np.sqrt(x64.var() + eps)
     return float(np.linalg.norm(got - want) / np.linalg.norm(want)), redo
+
+
+# ---- the tail of the train step through the C ABI (tests/test_09d_step_tail_gpu.py): fp64 reference builders of the fused losses and of
+# clip + AdamW, an integer emulation of the counter-based RNG of csrc/common.h, an fp32 emulation of the AdamW update and the launchers'
+# arithmetic restated; each is checked in tests/test_cpu.py
+def mse_gdl_ref(pred, gt, g_mse, g_gdl):
+    """fp64 MSELoss + GDL(alpha = 1) of pred, gt [planes, H, W] by the oracle's mse_loss / gdl_loss and autograd of g_mse * mse + g_gdl * gdl
+    (None = 0).  Returns mse, gdl (floats) and dpred [planes, H, W]."""
+    from oracle import vptr_oracle as O
+    pr = pred.double().unsqueeze(1).clone().requires_grad_(True)
+    gd = gt.double().unsqueeze(1)
+    lm, lg = O.mse_loss(gd, pr), O.gdl_loss(gd, pr)
+    (float(g_mse or 0.0) * lm + float(g_gdl or 0.0) * lg).backward()
+    return {"mse": float(lm.detach()), "gdl": float(lg.detach()), "dpred": pr.grad.squeeze(1)}
+
+
+def gdl_sign_disagreements(pred, gt):
+    """how many sign arguments of the GDL gradient (|gd| - |pd| and pd of every vertical and horizontal pair) have another sign evaluated in
+    fp32 than in fp64: the gradient is a sum of signs, so only inputs for which this is 0 let every element be compared"""
+    def args(p, g):
+        pdh, gdh = p[:, 1:, :] - p[:, :-1, :], g[:, 1:, :] - g[:, :-1, :]
+        pdw, gdw = p[:, :, :-1] - p[:, :, 1:], g[:, :, :-1] - g[:, :, 1:]
+        return [gdh.abs() - pdh.abs(), pdh, gdw.abs() - pdw.abs(), pdw]
+    return sum(int((torch.sign(a) != torch.sign(b).float()).sum()) for a, b in zip(args(pred.float(), gt.float()), args(pred.double(), gt.double())))
+
+
+def nce_ref(g, p, frames, L, tau, gout):
+    """fp64 reference of vptr_nce_fwd / _bwd on token-major g, p [frames * L, C]: F.normalize(p = 2, dim = channel) + the oracle's bipatch_nce
+    (the frame's L tokens as an L x 1 patch grid), autograd of gout * loss.  Returns loss, dg, dp and the scratch sections the forward leaves:
+    inv [2 R] (1 / max(|x|, 1e-12), rows of g first), S [frames, L, L] (scores / tau), rlse, clse [frames, L] (log-sum-exp of rows / columns)."""
+    import torch.nn.functional as F
+    from oracle import vptr_oracle as O
+    C = g.shape[1]
+    gd, pd = g.double().clone().requires_grad_(True), p.double().clone().requires_grad_(True)
+
+    def as5(t):
+        return t.reshape(1, frames, L, 1, C).permute(0, 1, 4, 2, 3)
+    loss = O.bipatch_nce(F.normalize(as5(gd), p=2.0, dim=2), F.normalize(as5(pd), p=2.0, dim=2), tau)
+    (float(gout) * loss).backward()
+    with torch.no_grad():
+        inv = 1.0 / torch.cat([gd.norm(dim=1), pd.norm(dim=1)]).clamp_min(1e-12)
+        gh, ph = (gd * inv[:frames * L, None]).view(frames, L, C), (pd * inv[frames * L:, None]).view(frames, L, C)
+        S = gh @ ph.transpose(1, 2) / tau
+    return {"loss": float(loss.detach()), "dg": gd.grad, "dp": pd.grad, "inv": inv, "S": S, "rlse": torch.logsumexp(S, 2), "clse": torch.logsumexp(S, 1)}
+
+
+def f32(x):
+    """the value a float argument of the C ABI has on the other side"""
+    return float(np.float32(x))
+
+
+def adamw_ref(p, g, m, v, step, lr, b1, b2, eps, wd, sumsq=None, max_norm=1.0, grad_scale=1.0, abi_hyper=True):
+    """one step of torch.optim.AdamW (decoupled decay, bias correction) with clip_grad_norm_ folded in, evaluated in fp64 on the fp32 state:
+    g' = g * grad_scale; with sumsq (the sum of squares of the UNSCALED gradients, as vptr_sumsq leaves it) g' *= min(1, max_norm /
+    (|g'| + 1e-6)); then torch's formulas.  abi_hyper: the hyper-parameters rounded to fp32 as vptr_adamw receives them (otherwise the
+    doubles torch.optim.AdamW itself works with).  Returns fp64 p, m, v."""
+    h = f32 if abi_hyper else float
+    lr, b1, b2, eps, wd, max_norm, grad_scale = (h(x) for x in (lr, b1, b2, eps, wd, max_norm, grad_scale))
+    gd = g.double() * grad_scale
+    if sumsq is not None:
+        gd = gd * min(1.0, max_norm / (float(sumsq) ** 0.5 * grad_scale + 1e-6))
+    pd = p.double() * (1.0 - lr * wd)
+    md = b1 * m.double() + (1.0 - b1) * gd
+    vd = b2 * v.double() + (1.0 - b2) * gd * gd
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    pd = pd - (lr / bc1) * md / (vd.sqrt() / bc2 ** 0.5 + eps)
+    return pd, md, vd
+
+
+def adamw_f32_emulation(p, g, m, v, step, lr, b1, b2, eps, wd, coef=1.0):
+    """the formula of adamw_kernel in fp32 (numpy, one rounding per operation; coef: the clip coefficient times grad_scale the raw gradient is
+    multiplied by), with bias corrections free of cancellation: 1 - b^k = -expm1(k log1p(b - 1)).  What a correct fp32 evaluation of the
+    update is expected to reach against adamw_ref."""
+    F = np.float32
+    lr, b1, b2, eps, wd, k = (F(x) for x in (lr, b1, b2, eps, wd, step))
+    pi, gi, mi, vi = (t.detach().numpy().astype(F) for t in (p, g, m, v))
+    gi = gi * F(coef)
+    bc1, bc2 = -np.expm1(k * np.log1p(b1 - F(1))), -np.expm1(k * np.log1p(b2 - F(1)))
+    assert bc1.dtype == F and bc2.dtype == F
+    pi = pi * (F(1) - lr * wd)
+    mi = b1 * mi + (F(1) - b1) * gi
+    vi = b2 * vi + ((F(1) - b2) * gi) * gi
+    denom = np.sqrt(vi) * (F(1) / np.sqrt(bc2)) + eps
+    pi = pi - (lr / bc1) * mi / denom
+    assert pi.dtype == F and mi.dtype == F and vi.dtype == F
+    return torch.from_numpy(pi), torch.from_numpy(mi), torch.from_numpy(vi)
+
+
+M32 = 0xFFFFFFFF
+
+
+def _mul32(x, c):
+    """(x * c) mod 2^32 for 0 <= x, c < 2^32 on Python ints or int64 tensors without leaving 63 bits"""
+    return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & M32
+
+
+def mix32_emu(x):
+    """vptr_mix32 (csrc/common.h)"""
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def hash3_emu(seed, site, idx):
+    """vptr_hash3 (csrc/common.h): seed a Python int read as uint64, site a Python int read as uint32, idx an int64 tensor of element indices
+    below 2^63.  Returns the 32-bit words as an int64 tensor."""
+    seed, site = int(seed) & 0xFFFFFFFFFFFFFFFF, int(site) & M32
+    key = mix32_emu((seed & M32) ^ mix32_emu(((seed >> 32) + _mul32((site + 1) & M32, 0x9E3779B9)) & M32))
+    idx = torch.as_tensor(idx, dtype=torch.int64)
+    return mix32_emu((((idx & M32) ^ key) + _mul32(idx >> 32, 0xC2B2AE35)) & M32)
+
+
+def drop_scale_emu(seed, site, idx, p):
+    """vptr_drop_scale: fp32 1 / (1 - p) where the element's word reaches the threshold uint32(p * 2^32), else 0 (p as the ABI's float)"""
+    pf = np.float32(p)
+    thr = int(float(pf) * 4294967296.0)
+    keep = float(np.float32(1.0) / (np.float32(1.0) - pf))
+    return torch.where(hash3_emu(seed, site, idx) >= thr, keep, 0.0).float()
+
+
+def droppath_emu(keep, maxcount, seed, site0):
+    """vptr_droppath_scales: out[r][k] = floor(keep[r] + u) / keep[r] in fp32 with u = (hash3(seed, site0 + r, k) >> 8) / 2^24"""
+    out = []
+    for r, kp in enumerate(keep.float().tolist()):
+        u = (hash3_emu(seed, int(site0) + r, torch.arange(maxcount)) >> 8).float() * (1.0 / 16777216.0)
+        kt = torch.tensor(kp, dtype=torch.float32)
+        out.append(torch.floor(kt + u) / kt)
+    return torch.stack(out)
+
+
+def step_tail_class(op, **g):
+    """the launch class of a call of the step's tail, restated from the launchers (csrc/losses.hip, csrc/elementwise.hip):
+    "mse_gdl" (planes, H, W): bands of 16 rows, partials = workgroups of the forward, rows of the last band, trips of a workgroup's element loop
+        and of the final kernel's loop over the partials, workgroups of the backward, scratch floats;
+    "nce" (frames, L, C): NV instantiation of the backward (or "reject"), its dynamic LDS bytes and grid, 64-row blocks, dead rows of the last
+        one, 16-token chunks and whether the last is partial, trips of the final kernel, whether the scores' channel guard is live, scratch floats;
+    "sumsq" (n, aligned): workgroups, unrolled trips, full single-float4 trips, threads of a partial trip, scalar tail (all-scalar trips if not
+        aligned);
+    "adamw" (n, aligned): workgroups, float4 trips, scalar-tail elements (or the trips of the all-scalar path)."""
+    cdiv = lambda a, b: (a + b - 1) // b
+    if op == "mse_gdl":
+        planes, H, W = g["planes"], g["H"], g["W"]
+        if planes <= 0 or H < 2 or W < 2:
+            return {"kernel": "reject"}
+        bands = cdiv(H, 16)
+        return {"bands": bands, "partials": planes * bands, "last_band_rows": H - 16 * (bands - 1), "band_trips": cdiv(min(H, 16) * W, 256),
+                "final_trips": cdiv(planes * bands, 256), "bwd_blocks": cdiv(planes * H * W, 256), "scratch": planes * bands * 3}
+    if op == "nce":
+        frames, L, C = g["frames"], g["L"], g["C"]
+        R, nb, C4 = frames * L, cdiv(L, 64), cdiv(C, 4)
+        out = {"nb": nb, "dead_rows": nb * 64 - L, "chunks": cdiv(L, 16), "partial_chunk": L % 16 != 0, "final_trips": cdiv(frames, 256),
+               "channel_guard": C % 16 != 0, "scratch": R * (4 + L) + frames, "fwd_grid": frames * nb * nb}
+        if C > 640 or C % 4:
+            out["nv"] = "reject"
+            return out
+        out["nv"] = 4 if C4 <= 16 else (16 if C4 <= 64 else (34 if C4 <= 136 else 40))
+        out["lds_bytes"], out["bwd_grid"] = (64 * 17 + 16 * C4 * 4) * 4, frames * nb * 2
+        return out
+    n, aligned = g["n"], g.get("aligned", True)
+    if op == "sumsq":
+        blocks = min(cdiv(n, 1024), 256)                # workgroups of 1024 threads
+        stride, n4 = blocks * 1024, n // 4
+        if not aligned:
+            return {"blocks": blocks, "scalar_trips": cdiv(n, stride)}
+        unrolled = 0                                   # thread 0 of workgroup 0 takes the most trips of every loop
+        while unrolled * 4 * stride + 3 * stride < n4:
+            unrolled += 1
+        rest = n4 - unrolled * 4 * stride              # float4 left to the single loop: `rest // stride` full trips, then `rest % stride` threads
+        return {"blocks": blocks, "unrolled": unrolled, "singles": max(rest, 0) // stride, "partial_threads": max(rest, 0) % stride, "tail": n - 4 * n4}
+    assert op == "adamw", op
+    blocks = min((n // 4 + 255) // 256 + 1, 4096)
+    stride = blocks * 256
+    if not aligned:
+        return {"blocks": blocks, "vec_trips": 0, "scalar_trips": cdiv(n, stride), "tail": n}
+    return {"blocks": blocks, "vec_trips": cdiv(n // 4, stride), "scalar_trips": 1 if n % 4 else 0, "tail": n % 4}
+
+
+def nce_f32_emulation(g, p, frames, L, tau, gout):
+    """vptr_nce_fwd / _bwd in torch fp32 in the kernels' operation order (inverse norms, scores scaled by both and by 1 / tau and STORED in fp32,
+    fp32 log-sum-exps, per-frame fp32 loss partials added in double; coefficients exp(S - lse) with the diagonal's second term, the fp32
+    matrix product against the normalised other tokens, the normalisation's backward) with libm's exp / log.  What fp32 storage and
+    arithmetic alone cost against nce_ref (most where the softmax is saturated -- a small loss at a small temperature -- and lse - S cancels):
+    tests/test_cpu.py asserts that this stays inside the bars of every case, i.e. that they are reachable in fp32.  Returns loss (float), dg, dp."""
+    F = torch.float32
+    C, R = g.shape[1], frames * L
+    g, p = g.to(F), p.to(F)
+    inv_tau, go = torch.tensor(1.0, dtype=F) / torch.tensor(tau, dtype=F), torch.tensor(gout, dtype=F)
+    inv_g = 1.0 / (g * g).sum(1).sqrt().clamp_min(1e-12)
+    inv_p = 1.0 / (p * p).sum(1).sqrt().clamp_min(1e-12)
+    S = torch.einsum("fic,fjc->fij", g.view(frames, L, C), p.view(frames, L, C)) * (inv_g.view(frames, L, 1) * inv_tau) * inv_p.view(frames, 1, L)
+    rlse, clse = torch.logsumexp(S, 2), torch.logsumexp(S, 1)
+    diag = torch.diagonal(S, dim1=1, dim2=2)
+    loss = float(((rlse - 2.0 * diag).sum(1) + clse.sum(1)).double().sum() * 0.5 / R)
+    cmean, eye = torch.tensor(0.5, dtype=F) / R, torch.eye(L, dtype=F)
+    Mg = (torch.exp(S - rlse[:, :, None]) + eye * (torch.exp(S - clse[:, None, :]) - 2.0)) * cmean                     # [f, g token, p token]
+    Mp = (torch.exp(S - clse[:, None, :]) + eye * (torch.exp(S - rlse[:, :, None]) - 2.0)).transpose(1, 2) * cmean     # [f, p token, g token]
+    gh, ph = (g * inv_g[:, None]).view(frames, L, C), (p * inv_p[:, None]).view(frames, L, C)
+    out = []
+    for M, Y, x, iv in ((Mg, ph, g, inv_g), (Mp, gh, p, inv_p)):
+        acc = (M @ Y).reshape(R, C) * (go * inv_tau)
+        dot = (x * acc).sum(1) * iv
+        dot = torch.where(iv >= 1e12, torch.zeros_like(dot), dot)
+        out.append((acc - x * (iv * dot)[:, None]) * iv[:, None])
+    assert out[0].dtype == F and S.dtype == F
+    return loss, out[0], out[1]

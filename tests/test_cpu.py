@@ -1169,3 +1169,224 @@ def test_gelu_polynomial_leaves_room_for_the_fp16_rounding():
         return float((np.abs(got - ref) / (2.0 ** -22 * np.abs(ref) + 2.0 ** -24)).max())
     assert worst(coef) <= 1.0, worst(coef)
     assert worst([0.254829592, -0.284496736, 1.421413741, -1.453152027, 1.061405429]) > 3.0
+
+
+# ---- the tail of the train step through the C ABI (tests/test_09d_step_tail_gpu.py): reference builders, the sign condition of the GDL inputs,
+# launch classes, the fp32 emulation the AdamW bars come from, the RNG emulation's own properties, emulated cases ---------------------------------
+def test_step_tail_refs_are_the_oracle_and_torch_optim():
+    """helpers.nce_ref on token-major rows == F.normalize + the oracle's bipatch_nce on a real (N, T, C, h, w) patch grid; helpers.adamw_ref with
+    the double hyper-parameters == clip_grad_norm_ on the scaled gradients + one torch.optim.AdamW step on fp64 parameters from the same
+    state, at 1e-12, for the clip absent / active / inactive, grad_scale 0.25 and both weight decays"""
+    import torch.nn.functional as Fn
+    import step_tail_cases as C
+    from helpers import adamw_ref, nce_ref
+    frames, h, w, Cc, tau = 3, 2, 5, 12, 0.07
+    g, p = fill.rand_normal((frames * h * w, Cc), 51), fill.rand_normal((frames * h * w, Cc), 52)
+    gd, pd = g.double().requires_grad_(True), p.double().requires_grad_(True)
+
+    def as5(t):
+        return t.reshape(1, frames, h, w, Cc).permute(0, 1, 4, 2, 3)
+    loss = O.bipatch_nce(Fn.normalize(as5(gd), p=2.0, dim=2), Fn.normalize(as5(pd), p=2.0, dim=2), tau)
+    (1.3 * loss).backward()
+    ref = nce_ref(g, p, frames, h * w, tau, 1.3)
+    loss = loss.detach()
+    assert abs(ref["loss"] - float(loss)) < 1e-12 and rel(ref["dg"], gd.grad) < 1e-12 and rel(ref["dp"], pd.grad) < 1e-12
+    S = ref["S"]
+    part = (ref["rlse"] + ref["clse"] - 2.0 * torch.diagonal(S, dim1=1, dim2=2)).sum()
+    assert abs(float(part) * 0.5 / (frames * h * w) - float(loss)) < 1e-12           # the sections are the ones the loss is made of
+
+    for k in (1, 4):
+        for case, (max_norm, gs) in C.ADAMW_CLIP.items():
+            for wd in C.ADAMW_WD:
+                p0, g0, m0, v0 = C.adamw_inputs(C.ADAMW_N, k, 0.9, 0.999)
+                pr = p0.double().clone().requires_grad_(True)
+                opt = torch.optim.AdamW([pr], lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=wd)
+                opt.state[pr] = {"step": torch.tensor(float(k - 1), dtype=torch.float64), "exp_avg": m0.double().clone(), "exp_avg_sq": v0.double().clone()}
+                pr.grad = g0.double() * gs
+                if max_norm is not None:
+                    torch.nn.utils.clip_grad_norm_([pr], max_norm)
+                opt.step()
+                sumsq = None if max_norm is None else float((g0.double() ** 2).sum())
+                got = adamw_ref(p0, g0, m0, v0, k, 1e-3, 0.9, 0.999, 1e-8, wd, sumsq, 1.0 if max_norm is None else max_norm, gs, abi_hyper=False)
+                st = opt.state[pr]
+                assert rel(got[0] - p0.double(), pr.detach() - p0.double()) < 1e-12, (k, case, wd)
+                assert rel(got[1], st["exp_avg"]) < 1e-12 and rel(got[2], st["exp_avg_sq"]) < 1e-12, (k, case, wd)
+
+
+def test_step_tail_gdl_inputs_have_no_fragile_sign():
+    """the GDL gradient is a sum of signs: for the seeded inputs of every geometry an fp32 and an fp64 evaluation of every sign argument agree, so
+    no element has to be excluded on the device; the forced ties are there (exact zeros among the arguments)"""
+    import step_tail_cases as C
+    from helpers import gdl_sign_disagreements
+    for geom in C.MSE_GEOMS:
+        pred, gt = C.mse_inputs(geom)
+        assert gdl_sign_disagreements(pred, gt) == 0, geom
+        k = C.mse_tie_rows(geom[1])
+        assert torch.equal(pred[:, :k], gt[:, :k]) and bool((pred[:, -1, 0] == pred[:, -1, 1]).all())
+        pdw, gdw = pred[:, :, :-1] - pred[:, :, 1:], gt[:, :, :-1] - gt[:, :, 1:]
+        assert bool(((gdw.abs() - pdw.abs()) == 0).any()) and bool(((pdw == 0) & (gdw != 0)).any())      # sign(0) in both factors
+
+
+def test_step_tail_cases_land_in_their_launch_classes():
+    """the launchers' arithmetic restated (helpers.step_tail_class): block counts, NV class, trips of each loop for every geometry of
+    tests/step_tail_cases.py"""
+    import step_tail_cases as C
+    from helpers import step_tail_class as cls
+    m = {g: cls("mse_gdl", planes=g[0], H=g[1], W=g[2]) for g in C.MSE_GEOMS}
+    assert (m[(300, 5, 3)]["partials"], m[(300, 5, 3)]["final_trips"]) == (300, 2)
+    assert (m[(2, 17, 9)]["bands"], m[(2, 17, 9)]["last_band_rows"]) == (2, 1)
+    assert (m[(1, 2, 2)]["partials"], m[(1, 2, 2)]["bwd_blocks"], m[(1, 2, 2)]["scratch"]) == (1, 1, 3)
+    assert (m[(2, 33, 300)]["bands"], m[(2, 33, 300)]["last_band_rows"], m[(2, 33, 300)]["band_trips"]) == (3, 1, 19)
+    assert (m[(7, 16, 16)]["bands"], m[(7, 16, 16)]["last_band_rows"], m[(7, 16, 16)]["band_trips"]) == (1, 16, 1)
+    assert (m[(40, 64, 64)]["partials"], m[(40, 64, 64)]["final_trips"]) == (160, 1)
+    assert all(v["final_trips"] == 1 for g, v in m.items() if g != (300, 5, 3))
+    for planes, H, W in C.MSE_REJECTS:
+        assert cls("mse_gdl", planes=planes, H=H, W=W) == {"kernel": "reject"}
+    for Cc in C.NCE_CHANNELS:
+        c = cls("nce", frames=2, L=35, C=Cc)
+        assert c["nv"] == C.NCE_NV[Cc] and c["lds_bytes"] <= 64 * 1024 and c["channel_guard"] == (Cc % 16 != 0), Cc
+        assert (c["nb"], c["dead_rows"], c["chunks"], c["partial_chunk"]) == (1, 29, 3, True)
+    assert {C.NCE_NV[c] for c in C.NCE_CHANNELS} == {4, 16, 34, 40} and sum(c % 16 != 0 for c in C.NCE_CHANNELS) >= 4
+    assert cls("nce", frames=2, L=35, C=644)["nv"] == "reject" and cls("nce", frames=2, L=35, C=6)["nv"] == "reject"
+    want = {(1, 1): (1, 63, 1, True, 1), (3, 64): (1, 0, 4, False, 1), (2, 80): (2, 48, 5, False, 1), (1, 130): (3, 62, 9, True, 1),
+            (2, 256): (4, 0, 16, False, 1), (300, 4): (1, 60, 1, True, 2)}
+    for (frames, L), w in want.items():
+        c = cls("nce", frames=frames, L=L, C=548)
+        assert (c["nb"], c["dead_rows"], c["chunks"], c["partial_chunk"], c["final_trips"]) == w, (frames, L)
+        assert c["scratch"] == frames * L * (4 + L) + frames and c["bwd_grid"] == frames * c["nb"] * 2
+    assert set(want) == set(C.NCE_GEOMS) and len(C.nce_cases()) == 2 * (len(C.NCE_CHANNELS) + 2 * len(C.NCE_GEOMS))
+    big = cls("sumsq", n=C.SUMSQ_BIG)
+    assert big == {"blocks": 256, "unrolled": 2, "singles": 2, "partial_threads": 1000, "tail": 2} and C.SUMSQ_BIG * 4 < 50e6
+    assert cls("sumsq", n=10007) == {"blocks": 10, "unrolled": 0, "singles": 0, "partial_threads": 2501, "tail": 3}       # test_00's size
+    assert cls("sumsq", n=3)["tail"] == 3 and cls("sumsq", n=1024)["tail"] == 0 and cls("sumsq", n=1023)["tail"] == 3
+    assert cls("sumsq", n=C.SUMSQ_BIG, aligned=False) == {"blocks": 256, "scalar_trips": 41}
+    a = cls("adamw", n=C.ADAMW_BIG)
+    assert a == {"blocks": 4096, "vec_trips": 2, "scalar_trips": 1, "tail": 3}
+    assert cls("adamw", n=10007) == {"blocks": 11, "vec_trips": 1, "scalar_trips": 1, "tail": 3}                             # test_00's size
+    assert cls("adamw", n=C.ADAMW_BIG, aligned=False) == {"blocks": 4096, "vec_trips": 0, "scalar_trips": 5, "tail": C.ADAMW_BIG}
+    assert [cls("adamw", n=n)["vec_trips"] for n in (1, 3, 4, 1027)] == [0, 0, 1, 1] and cls("adamw", n=1027)["blocks"] == 2
+    assert cls("adamw", n=C.ADAMW_N) == {"blocks": 5, "vec_trips": 1, "scalar_trips": 1, "tail": 3}
+
+
+def test_adamw_bars_come_from_a_cancellation_free_fp32_evaluation():
+    """helpers.adamw_f32_emulation (the kernel's formula in fp32 with 1 - b^k = -expm1(k log1p(b - 1))) on the inputs of the update-precision
+    cases: its rel-L2 distance to fp64 is about 1e-7 on the update, m and v at every step count, so the bars (5 x) sit at or below 1e-6.
+    The same evaluation with 1 - powf(b, k) is 3 to 60 times further from fp64 on the update at steps 2, 3 and 5 of betas (0.9, 0.999) -- the
+    subtraction cancels -- and exactly as close at step 1, where 1 - 0.999f is exact"""
+    import step_tail_cases as C
+    from helpers import adamw_f32_emulation, adamw_ref
+    F = np.float32
+    for betas in C.ADAMW_BETAS:
+        hyper = dict(C.HYPER, b1=betas[0], b2=betas[1])
+        for k in C.ADAMW_STEPS:
+            p, g, m, v = C.adamw_inputs(C.ADAMW_N, k, betas[0], betas[1])
+            state = (torch.zeros_like(p), g, m, v)
+            bars, dist, want = C.adamw_bars(state, k, hyper, None, None, 1.0)
+            print("adamw emulation step %d betas %g/%g: update %.3e m %.3e v %.3e" % ((k,) + betas + tuple(dist)))
+            # (b1 = 0.5 at step 1: m = 0.5 g is exact in any binary format, its distance and its bar are 0)
+            assert all(d < 2e-7 for d in dist) and dist[0] > 0.0 and all(b == 5.0 * d for b, d in zip(bars, dist)), (k, betas, dist)
+            # the cancelling form: the update scales with sqrt(bc2) / bc1
+            bc = [F(1) - np.power(F(b), F(k), dtype=F) for b in betas]
+            exact = [1.0 - float(F(b)) ** k for b in betas]
+            scale = (float(bc[1]) / exact[1]) ** 0.5 / (float(bc[0]) / exact[0])
+            naive = rel(adamw_f32_emulation(*state, k, **hyper)[0].double() * scale, want[0])
+            print("    with 1 - powf(b, k): update %.3e" % naive)
+            if k == 1:
+                assert scale == 1.0
+            if betas == (0.9, 0.999) and k in (2, 3, 5):
+                assert naive > bars[0], (k, naive, bars[0])
+
+
+def test_hash_emulation_properties():
+    """helpers.hash3_emu / drop_scale_emu / droppath_emu (the integer emulation of csrc/common.h the device is compared with bit for bit): the
+    keep rate of 10^6 elements within 3 sigma of 1 - p; flipping one bit of the seed's low word, of its high word, of the site or of the
+    index flips 0.5 +- 0.02 of the 32 output bits on average (the two-multiply finaliser's avalanche bias is under 1 %, the mean over 20 000
+    x 32 bits has a sigma of 6e-4); the index's high word takes part; constants as in the source"""
+    from helpers import drop_scale_emu, droppath_emu, hash3_emu, mix32_emu
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vptr_amd", "csrc", "common.h")).read()
+    for const in ("0x7FEB352Du", "0x846CA68Bu", "0x9E3779B9u", "0xC2B2AE35u", "x >> 16; x *=", "x ^= x >> 15"):
+        assert const in src, const
+    assert mix32_emu(0) == 0 and mix32_emu(1) == mix32_emu(torch.tensor([1]))[0] and 0 < mix32_emu(1) < 1 << 32
+    seed, n = 0x9A3C5E7F12345678, 1000000
+    idx = torch.arange(n)
+    for p in (0.1, 0.5, 0.999):
+        s = drop_scale_emu(seed, 3, idx, p)
+        kept = float((s != 0).double().mean())
+        assert abs(kept - (1.0 - p)) < 3.0 * (p * (1.0 - p) / n) ** 0.5, (p, kept)
+        assert set(torch.unique(s).tolist()) == {0.0, float(np.float32(1) / (np.float32(1) - np.float32(p)))}
+    dp = droppath_emu(torch.tensor([0.9, 0.5, 1.0]), 100000, seed, 7)
+    for r, kp in enumerate((0.9, 0.5)):
+        assert abs(float((dp[r] != 0).double().mean()) - kp) < 3.0 * (kp * (1.0 - kp) / 100000) ** 0.5
+    assert bool((dp[2] == 1.0).all())
+
+    def flipped(a, b):
+        x = a ^ b
+        return float(sum(((x >> i) & 1).double().mean() for i in range(32)) / 32.0)
+    idx = torch.arange(20000) * 7919 + 11
+    base = hash3_emu(seed, 5, idx)
+    for bit in range(32):
+        for name, other in (("seed low", hash3_emu(seed ^ (1 << bit), 5, idx)), ("seed high", hash3_emu(seed ^ (1 << (32 + bit)), 5, idx)),
+                            ("site", hash3_emu(seed, 5 ^ (1 << bit), idx)), ("index", hash3_emu(seed, 5, idx ^ (1 << bit)))):
+            f = flipped(base, other)
+            assert 0.48 < f < 0.52, (name, bit, f)
+    assert not torch.equal(hash3_emu(seed, 5, idx + (1 << 32)), base) and 0.48 < flipped(hash3_emu(seed, 5, idx + (1 << 32)), base) < 0.52
+    assert hash3_emu(seed, 0xFFFFFFFF, idx).max() < 1 << 32 and torch.equal(hash3_emu(seed, -1, idx), hash3_emu(seed, 0xFFFFFFFF, idx))
+
+
+def test_nce_bars_are_reachable_in_fp32():
+    """helpers.nce_f32_emulation (fp32 storage and arithmetic in the kernels' order, libm's exp / log) stays inside test_00's bars -- loss 2e-6,
+    gradients 1e-5 -- for every case of tests/step_tail_cases.py, so no bar has to move.  The closest are the saturated softmaxes at tau 0.07,
+    where lse - S cancels: 300 x 4 x 548 (gradients at 0.86 - 0.89 of the bar) and 2 x 35 x 544 (loss at 0.68)"""
+    import step_tail_cases as C
+    worst = {"loss": (0.0, None), "dg": (0.0, None), "dp": (0.0, None)}
+    for case in C.nce_cases() + [(2, 35, 6, tau) for tau in C.NCE_TAUS]:
+        d = C.nce_emulation_distances(*case, 1.0)
+        for k, v in d.items():
+            assert v < (C.TOL_NCE if k == "loss" else C.TOL_NCE_GRAD), (case, k, v)
+            worst[k] = max(worst[k], (v, case))
+    print("nce fp32 emulation, worst distances:", worst)
+    assert worst["dg"][1] == (300, 4, 548, 0.07) and worst["dp"][1] == (300, 4, 548, 0.07) and worst["loss"][1] == (2, 35, 544, 0.07)
+
+
+@pytest.mark.parametrize("part", ["mse_gdl", "nce_channels", "nce_geoms", "sumsq", "adamw", "rng"])
+def test_step_tail_cases_against_emulation(part, capsys):
+    """the cases of tests/test_09d_step_tail_gpu.py against a CPU emulation of the entry points written from the header: argument order,
+    layouts, guards, scratch sizes, references and bars of the CASES, not the kernels"""
+    import step_tail_cases as C
+    be = C.EmuBackend()
+    if part == "mse_gdl":
+        for geom in C.MSE_GEOMS:
+            for variant in C.MSE_VARIANTS:
+                C.run_mse_gdl(be, geom, variant)
+        C.run_mse_gdl_rejects(be)
+    elif part == "nce_channels":
+        for frames, L, Cc, tau in C.nce_cases()[:2 * len(C.NCE_CHANNELS)]:
+            C.run_nce(be, frames, L, Cc, tau)
+        C.run_nce_c6(be)
+        C.run_nce_bwd_rejects(be)
+    elif part == "nce_geoms":
+        for frames, L, Cc, tau in C.nce_cases()[2 * len(C.NCE_CHANNELS):]:
+            C.run_nce(be, frames, L, Cc, tau)
+    elif part == "sumsq":
+        for n in C.SUMSQ_SIZES:
+            for aligned in (True, False):
+                C.run_sumsq(be, n, aligned)
+        for nws in C.SUMSQ_WS:
+            C.run_sumsq_ws(be, nws)
+        C.run_sumsq_rejects(be)
+    elif part == "adamw":
+        for case in C.ADAMW_LAUNCH:
+            C.run_adamw_launch(be, case)
+        C.run_adamw_paths_equal(be)
+        for case in C.ADAMW_CLIP:
+            for wd in C.ADAMW_WD:
+                C.run_adamw_clip(be, case, wd)
+        C.run_adamw_zero_grad(be)
+        for betas in C.ADAMW_BETAS:
+            for k in C.ADAMW_STEPS:
+                C.run_adamw_precision(be, k, betas)
+    else:
+        for n in C.DROP_SIZES:
+            C.run_dropout(be, n)
+        for maxcount in C.DROPPATH_COUNTS:
+            C.run_droppath(be, maxcount)
