@@ -58,7 +58,7 @@ int vptr_wgrad_kernel_counts(int* out_host, int n);
  * split_k >= 0 and get the plain grouped launch, which has no shared state.  Breaking the contract cannot hang or corrupt results
  * (destination adds are atomic, every wait is bounded) -- it costs bounded-spin time-outs, visible in vptr_wgrad_sync_stats.
  * The library itself reads four of the A/B switches of INTEGRATION.md's table: VPTR_WGRAD_SYNC ONCE, at the first launch that consults it;
- * VPTR_ATTN16 / VPTR_ATTN_MFMA / VPTR_ATTN16_FWD1 per launch (the tests switch attention families inside one process). */
+ * VPTR_ATTN16 / VPTR_ATTN_MFMA / VPTR_ATTN16_FWD1 per launch (the tests switch attention families inside one process; csrc/attn_route.h). */
 
 /* ------------------------------------------------------------------------------------------------
  * GEMM + fused epilogue on MFMA (bf16 inputs split from fp32 in the staging path, fp32 accumulate).
@@ -348,6 +348,19 @@ int vptr_tattn_fwd(const float* q, const float* k, const float* v, float* o, int
 int vptr_tattn_bwd(const float* q, const float* k, const float* v, const float* dout, float* dq, float* dk, float* dv,
                    int Nb, int Tq, int Tk, int HW, int C, int nh, int causal, float dropout_p, const uint64_t* seed_dev,
                    uint32_t site, float dq_scale /* as in vptr_winattn_bwd */, int p16, vptr_stream_t stream);
+
+/* Which kernel family the four calls above run for a problem, under the attention switches as the environment holds them at the time
+ * of the call (csrc/attn_route.h has the table and every condition; the launchers ask the same function).  Host-side only: no
+ * stream, no device work.  kind 0: ws x ws windows (Lq = Lk = ws * ws), 1: temporal (Lq = Tq, Lk = Tk, ws ignored); groups: windows
+ * (B * (H / ws) * (W / ws)) or N * HW pixels; aligned16: every tensor of the call is 16-byte aligned.  out[0 .. n) (HOST ints,
+ * 1 <= n <= 4) = family, the template pair a, b of the matrix-unit families (0, 0 otherwise), and one variant bit: attn16 -- the
+ * unmasked 16 x 16 instantiation; 16-token temporal vector kernels -- 4 pixels per wave with prefetch; attn_mfma -- more than one
+ * 16-row query block per problem. */
+enum { VPTR_ATTN_FAMILY_VECTOR = 0 /* generic fp32 vector kernels */, VPTR_ATTN_FAMILY_VECTOR16 = 1 /* 16-token fp32 vector kernels */,
+       VPTR_ATTN_FAMILY_A16_GEN1 = 2, VPTR_ATTN_FAMILY_A16_GEN2 = 3 /* attn16.hip, first / second generation */,
+       VPTR_ATTN_FAMILY_AM_PLAIN = 4, VPTR_ATTN_FAMILY_AM_SHARED = 5 /* attn_mfma.hip, plain / tile-sharing backward */ };
+int vptr_attn_route(int kind, int Lq, int Lk, int C, int nh, int ws, int causal, int64_t groups, int backward, int aligned16,
+                    int* out_host, int n);
 
 /* One decoding step of the CAUSAL temporal attention against a key / value cache (eval only: no mask, no dropout).
  * q, o: [rows, C], rows = N*H*W, one query per (sample, pixel), q pre-scaled by head_dim^-0.5.

@@ -30,13 +30,14 @@ def p16_decode(t):
 
 
 class Guarded:
-    """[rows, C] fp32 output inside a NaN-filled buffer with a guard of C floats (rounded up to 64 bytes) on both sides"""
+    """[rows, C] fp32 output inside a NaN-filled buffer with a guard of C floats (rounded up to 64 bytes) on both sides; shift: floats past the
+    16-byte boundary at which the output starts"""
 
-    def __init__(self, rows, C, dev, start=None):
-        self.g = -(-(C * 4) // 64) * 16
+    def __init__(self, rows, C, dev, start=None, shift=0):
+        self.g = -(-(C * 4) // 64) * 16 + shift
         self.buf = torch.full((2 * self.g + rows * C,), float("nan"), device=dev, dtype=torch.float32)
         self.out = self.buf[self.g: self.g + rows * C].view(rows, C)
-        assert self.out.data_ptr() % 16 == 0
+        assert self.out.data_ptr() % 16 == 4 * shift
         if start is not None:
             self.out.copy_(start)
 
@@ -230,13 +231,26 @@ def _to(be, *ts):
     return [None if t is None else t.to(be.dev) for t in ts]
 
 
+def _shifted(t, shift):
+    """t itself (shift 0), or a copy of it that starts `shift` floats past a 16-byte boundary"""
+    if not shift:
+        return t
+    buf = torch.empty(t.numel() + 4, device=t.device, dtype=t.dtype)
+    out = buf[shift: shift + t.numel()].view(t.shape).copy_(t)
+    assert out.data_ptr() % 16 == 4 * shift and out.is_contiguous()
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------ one call each
-def win_call(be, ins, B, H, W, C, nh, ws, p16, p=0.0, seed=None, table_start=None, want_dtable=True, entry="bwd", workspace=None, ws_floats=0):
+def win_call(be, ins, B, H, W, C, nh, ws, p16, p=0.0, seed=None, table_start=None, want_dtable=True, entry="bwd", workspace=None, ws_floats=0,
+             shift=0):
     """vptr_winattn_fwd + one backward entry point on guarded outputs; returns the decoded o, dq, dk, dv (and dtable) on the CPU.
-    table_start: initial contents of the table gradient (None: zeros); want_dtable False: dbias_table == NULL"""
+    table_start: initial contents of the table gradient (None: zeros); want_dtable False: dbias_table == NULL; shift: q, k, v, dout and the four
+    outputs start that many floats past a 16-byte boundary"""
     q, k, v, go, table, idx = _to(be, *ins)
+    q, k, v, go = (_shifted(t, shift) for t in (q, k, v, go))
     n, ntab, scale = B * H * W, (2 * ws - 1) ** 2, (C // nh) ** -0.5
-    o, dq, dk, dv = (Guarded(n, C, be.dev) for _ in range(4))
+    o, dq, dk, dv = (Guarded(n, C, be.dev, shift=shift) for _ in range(4))
     be.call("winattn_fwd", q, k, v, table, idx, o.out, B, H, W, C, nh, ws, p, seed, DROP_SITE, int(p16))
     dt = None
     if table is not None and want_dtable:
@@ -252,10 +266,10 @@ def win_call(be, ins, B, H, W, C, nh, ws, p16, p=0.0, seed=None, table_start=Non
     return out
 
 
-def t_call(be, ins, N, Tq, Tk, HW, C, nh, causal, p16, p=0.0, seed=None):
-    q, k, v, go = _to(be, *ins)
-    o, dq = Guarded(N * Tq * HW, C, be.dev), Guarded(N * Tq * HW, C, be.dev)
-    dk, dv = Guarded(N * Tk * HW, C, be.dev), Guarded(N * Tk * HW, C, be.dev)
+def t_call(be, ins, N, Tq, Tk, HW, C, nh, causal, p16, p=0.0, seed=None, shift=0):
+    q, k, v, go = (_shifted(t, shift) for t in _to(be, *ins))
+    o, dq = Guarded(N * Tq * HW, C, be.dev, shift=shift), Guarded(N * Tq * HW, C, be.dev, shift=shift)
+    dk, dv = Guarded(N * Tk * HW, C, be.dev, shift=shift), Guarded(N * Tk * HW, C, be.dev, shift=shift)
     be.call("tattn_fwd", q, k, v, o.out, N, Tq, Tk, HW, C, nh, int(causal), p, seed, DROP_SITE, int(p16))
     be.call("tattn_bwd", q, k, v, go, dq.out, dk.out, dv.out, N, Tq, Tk, HW, C, nh, int(causal), p, seed, DROP_SITE, (C // nh) ** -0.5, int(p16))
     return {"op": "tattn", "p16": bool(p16), "o": o.result(p16), "dq": dq.result(p16), "dk": dk.result(p16), "dv": dv.result(p16)}
@@ -346,6 +360,12 @@ def run_parity(be, geom, nh, C):
         got16 = geom_call(be, geom, ins, nh, C, True)
         compare(got16, ref)
         compare_p16(got16, got)
+
+
+def run_unaligned(be, geom, nh, C):
+    """fp32 outputs with q, k, v, dout, o, dq, dk, dv all 8 bytes past a 16-byte boundary, same bars"""
+    ins, ref = geom_inputs(geom, nh, C)
+    compare(geom_call(be, geom, ins, nh, C, False, shift=2), ref)
 
 
 def problem_dims(geom, nh):

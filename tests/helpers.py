@@ -287,7 +287,8 @@ class attn_kernel_mode:
     most 16 tokens on the MFMA kernels of attn16.hip -- forward without LDS, backward of the second generation when C % 4 == 0; larger ones on the
     LDS-staged MFMA kernels of attn_mfma.hip), "attn16" = VPTR_ATTN16=2 (attn16.hip forward + its first-generation backward), "attn16fwd" =
     VPTR_ATTN16=4 (attn16.hip forward, fp32 vector backward), "mfma" = VPTR_ATTN_MFMA=2 (attn_mfma.hip wherever it covers the geometry) and
-    "vector" = VPTR_ATTN_MFMA=0 (the fp32 vector kernels of attn.hip everywhere); the variables' earlier values come back on exit"""
+    "vector" = VPTR_ATTN_MFMA=0 (the fp32 vector kernels of attn.hip everywhere); the variables' earlier values come back on exit.  The table of
+    the switches is in csrc/attn_route.h; attn_route below asks the library which family a call reaches"""
 
     def __init__(self, mode):
         assert mode in ATTN_MODES, mode
@@ -319,6 +320,27 @@ def current_attn_mode():
     if m is not None and int(m) != 1:
         return "mfma" if int(m) == 2 else "vector"
     return {None: "default", "1": "default", "2": "attn16", "4": "attn16fwd"}.get(e, "VPTR_ATTN16=%s" % e)
+
+
+ATTN_FAMILIES = ("vector", "vector16", "a16_gen1", "a16_gen2", "am_plain", "am_shared")     # VPTR_ATTN_FAMILY_* of include/vptr_hip.h, in order
+
+
+def attn_route(kind, Lq, Lk, C, nh, ws=0, causal=0, groups=1, backward=0, aligned16=1):
+    """vptr_attn_route (host-side, no GPU) under the switches the environment holds right now: (family name, (a, b), variant)"""
+    import ctypes
+    from vptr_amd import _lib
+    out = (ctypes.c_int * 4)(-1, -1, -1, -1)
+    _lib.check(_lib.lib.vptr_attn_route(kind, Lq, Lk, C, nh, ws, int(causal), groups, int(backward), int(aligned16), out, 4), "vptr_attn_route")
+    return ATTN_FAMILIES[out[0]], (out[1], out[2]), out[3]
+
+
+def attn_geom_route(geom, nh, C, backward, aligned16=1):
+    """attn_route of a geometry of tests/attn_abi_cases.py: ("win", B, H, W, ws, bias) or ("t", N, Tq, Tk, HW, causal)"""
+    if geom[0] == "win":
+        _, B, H, W, ws, _ = geom
+        return attn_route(0, ws * ws, ws * ws, C, nh, ws, 0, B * (H // ws) * (W // ws), backward, aligned16)
+    _, N, Tq, Tk, HW, causal = geom
+    return attn_route(1, Tq, Tk, C, nh, 0, causal, N * HW, backward, aligned16)
 
 
 # (N, Tq, Tk, H, W, ws, C, nh) of the TSLMA core tests: the K64 model's own geometry (head dim 66: 115 KB of dynamic LDS in the backward, 7 key

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import attn_abi_cases as A
-from helpers import ATTN_MODES, TS_GEOMS, attn_kernel_mode
+from helpers import ATTN_MODES, TS_GEOMS, attn_geom_route, attn_kernel_mode
 
 pytestmark = pytest.mark.gpu
 
@@ -104,6 +104,17 @@ def test_table_gradient_workspace(be, nh, C):
     gradient, as the header promises), a workspace one float too small (atomic fallback) and NULL"""
     with attn_kernel_mode("default"):
         A.run_workspace_contract(be, A.LAUNCH_CASES["win4_1547win_loop_wpb8_tail"][0], nh, C)
+
+
+@pytest.mark.parametrize("geom,nh,C", [("win4_B3_8x8_bias", 2, 48), ("t5x5_causal", 8, 528)])
+def test_unaligned_tensors_take_first_generation(be, geom, nh, C):
+    """default routing, fp32 outputs, every tensor 8 bytes past a 16-byte boundary: the second-generation attn16 kernels need 16-byte aligned
+    rows, so the call falls back to the first generation, forward and backward (vptr_attn_route says so), and meets the same bars"""
+    with attn_kernel_mode("default"):
+        for backward in (0, 1):
+            assert attn_geom_route(A.GEOMS[geom], nh, C, backward, aligned16=0)[0] == "a16_gen1"
+            assert attn_geom_route(A.GEOMS[geom], nh, C, backward, aligned16=1)[0] == "a16_gen2"
+        A.run_unaligned(be, A.GEOMS[geom], nh, C)
 
 
 @pytest.mark.parametrize("N,Tq,Tk,H,W,ws,C,nh", [TS_GEOMS[0], TS_GEOMS[1], TS_GEOMS[5]])

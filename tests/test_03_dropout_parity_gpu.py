@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import ZERO_CLASS, analytic_zero, build_transformer, grad_floor, rel
+from helpers import ZERO_CLASS, analytic_zero, attn_kernel_mode, build_transformer, grad_floor, rel
 from oracle import fill
 from oracle import vptr_oracle as O
 
@@ -29,17 +29,10 @@ def _scale(ops, dev, seed, site, shape, p=P_DROP):
 
 @pytest.fixture(params=["default", "mfma"])
 def attn_kernels(request):
-    """the attention-probability masks through both kernel families (16-token problems default to the fp32 vector kernels;
-    VPTR_ATTN_MFMA=2 sends them through the matrix-core kernels, which must hash the same element indices)"""
-    import os
-    old = os.environ.get("VPTR_ATTN_MFMA")
-    if request.param == "mfma":
-        os.environ["VPTR_ATTN_MFMA"] = "2"
-    yield request.param
-    if old is None:
-        os.environ.pop("VPTR_ATTN_MFMA", None)
-    else:
-        os.environ["VPTR_ATTN_MFMA"] = old
+    """the attention-probability masks through both matrix-unit kernel families (helpers.attn_kernel_mode: the 16-token problems of this model
+    run on attn16.hip by default and on attn_mfma.hip in mode "mfma"; both must hash the same element indices)"""
+    with attn_kernel_mode(request.param) as mode:
+        yield mode
 
 
 @pytest.mark.parametrize("far", [False, True])

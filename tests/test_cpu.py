@@ -159,6 +159,90 @@ def test_wgrad_kernel_counts_query():
     assert r.stdout.strip().splitlines()[-1] == "[0, 0, 0, 0, 0]", r.stdout
 
 
+# vptr_attn_route: expected routes transcribed from the launchers' cascade as it stood before csrc/attn_route.h took it over (vptr_attn_mfma_ok,
+# vptr_attn16_ok, the heads of vptr_attn16_fwd / _bwd, rows16_fits and the prefetch split of the entry points), never from the code under test.
+# Columns: the geometries below in order, "forward/backward"; g1 / g2 = attn16 first / second generation, amp / ams = attn_mfma plain / tile-sharing
+# backward, v16 / vec = 16-token / generic fp32 vector kernels; "+" = the variant bit (attn16: unmasked 16 x 16; v16: prefetch; attn_mfma: Lq > 16)
+ROUTE_GEOMS = {"win4": (0, 16, 16, 4, 0, 12), "win8": (0, 64, 64, 8, 0, 2), "win2": (0, 4, 4, 2, 0, 12), "t5_causal": (1, 5, 5, 0, 1, 18),
+               "t3x7": (1, 3, 7, 0, 0, 18), "t20_causal": (1, 20, 20, 0, 1, 5), "t40x33": (1, 40, 33, 0, 0, 3), "t10_1551px": (1, 10, 10, 0, 0, 1551),
+               "t16_1551px": (1, 16, 16, 0, 0, 1551), "t17": (1, 17, 17, 0, 0, 18)}     # kind, Lq, Lk, ws, causal, groups
+ROUTE_HEADS = {24: (2, 48), 66: (8, 528), 94: (2, 188), 96: (2, 192), 98: (2, 196), 22: (2, 44), 18: (3, 54)}      # head dim: (nh, C); C = 54: C % 4 != 0
+ROUTE_PAIRS = {24: (1, 2), 66: (3, 5), 94: (3, 6), 96: (3, 6), 22: (1, 2), 18: (1, 2)}   # of the matrix-unit families (hd 94: second-generation span 96)
+ROUTE_ENVS = {"default": {}, "attn16": {"VPTR_ATTN16": "2"}, "attn16fwd": {"VPTR_ATTN16": "4"}, "mfma": {"VPTR_ATTN_MFMA": "2"},
+              "vector": {"VPTR_ATTN_MFMA": "0"}, "fwd1": {"VPTR_ATTN16_FWD1": "1"}}
+_BIG = "amp+/ams+"
+_OVER = "vec/vec vec/vec vec/vec v16/v16 v16/v16 vec/vec vec/vec v16/v16 v16/v16 vec/vec"      # hd 98; hd 94 / 96 on the vector kernels (rows16_fits fails)
+_G1_VEC = "g1+/v16 %s vec/vec g1/v16 g1/v16 %s %s g1/v16+ g1+/v16+ %s" % ((_BIG,) * 4)         # first-generation forward, 16-token vector backward
+ROUTE_TABLE = {
+    "default": {(24, 66, 94, 96, 22): "g2+/g2+ %s vec/vec g2/g2 g2/g2 %s %s g2/g2 g2+/g2+ %s" % ((_BIG,) * 4), (18,): _G1_VEC, (98,): _OVER},
+    "attn16": {(24, 66, 94, 96, 22, 18): "g1+/g1+ %s vec/vec g1/g1 g1/g1 %s %s g1/g1 g1+/g1+ %s" % ((_BIG,) * 4), (98,): _OVER},
+    "attn16fwd": {(24, 22, 18): _G1_VEC, (66,): "g1+/v16 %s vec/vec g1/v16 g1/v16 %s %s g1/v16+ g1+/v16 %s" % ((_BIG,) * 4),     # 16 * 34 = 544 > 384
+                  (94, 96): "g1+/vec %s vec/vec g1/v16 g1/v16 %s %s g1/v16 g1+/v16 %s" % ((_BIG,) * 4), (98,): _OVER},
+    "mfma": {(24, 66, 94, 96, 22, 18): "amp/amp %s amp/amp amp/amp amp/amp %s %s amp/amp amp/amp %s" % ((_BIG,) * 4), (98,): _OVER},
+    "vector": {(24, 22, 18): "v16/v16 vec/vec vec/vec v16/v16 v16/v16 vec/vec vec/vec v16+/v16+ v16+/v16+ vec/vec",
+               (66,): "v16/v16 vec/vec vec/vec v16/v16 v16/v16 vec/vec vec/vec v16+/v16+ v16/v16 vec/vec", (94, 96, 98): _OVER},
+    "fwd1": {(24, 66, 94, 96, 22): "g1+/g2+ %s vec/vec g1/g2 g1/g2 %s %s g1/g2 g1+/g2+ %s" % ((_BIG,) * 4), (18,): _G1_VEC, (98,): _OVER},
+}
+_ROUTE_CHILD = """
+import ctypes, json, os, sys
+from vptr_amd import _lib
+job = json.loads(sys.argv[1])
+res = []
+for env, calls in job:
+    for k in ("VPTR_ATTN_MFMA", "VPTR_ATTN16", "VPTR_ATTN16_FWD1"):
+        os.environ.pop(k, None)
+    os.environ.update(env)
+    for c in calls:
+        out = (ctypes.c_int * 4)(-1, -1, -1, -1)
+        assert _lib.lib.vptr_attn_route(*c, out, 4) == 0, c
+        res.append(list(out))
+out = (ctypes.c_int * 5)(*([-7] * 5))
+for n in (0, 5, -1):
+    assert _lib.lib.vptr_attn_route(0, 16, 16, 48, 2, 4, 0, 12, 0, 1, out, n) != 0 and b"1 .. 4" in _lib.lib.vptr_last_error(), n
+assert _lib.lib.vptr_attn_route(0, 16, 16, 48, 2, 4, 0, 12, 0, 1, None, 4) != 0 and list(out) == [-7] * 5
+assert _lib.lib.vptr_attn_route(0, 16, 16, 48, 2, 4, 0, 12, 0, 1, out, 2) == 0 and list(out) == [3, 1, -7, -7, -7]
+print(json.dumps(res))
+"""
+
+
+def test_attn_route_table():
+    """vptr_attn_route (which kernel family serves an attention call) in a child process, the switches set per mode: the five ATTN_MODES and
+    VPTR_ATTN16_FWD1=1 over seven head classes x ten geometries x forward / backward against the table above, the unaligned fallback, a tensor of
+    2^31 elements; n outside 1 .. 4 and a null output are rejected"""
+    import json
+    import subprocess
+    from helpers import ATTN_FAMILIES, ATTN_MODES, attn_kernel_mode
+    fam = {"vec": "vector", "v16": "vector16", "g1": "a16_gen1", "g2": "a16_gen2", "amp": "am_plain", "ams": "am_shared"}
+    job, want = [], []
+    for mode, env in ROUTE_ENVS.items():
+        if mode in ATTN_MODES:           # the helper the GPU tests switch families with sets the same variables
+            with attn_kernel_mode(mode):
+                assert {k: os.environ.get(k) for k in ("VPTR_ATTN_MFMA", "VPTR_ATTN16")} == {"VPTR_ATTN_MFMA": env.get("VPTR_ATTN_MFMA"),
+                                                                                              "VPTR_ATTN16": env.get("VPTR_ATTN16")}
+        rows = {hd: row.split() for hds, row in ROUTE_TABLE[mode].items() for hd in hds}
+        assert sorted(rows) == sorted(ROUTE_HEADS) and all(len(r) == len(ROUTE_GEOMS) for r in rows.values())
+        calls = []
+        for hd, (nh, C) in ROUTE_HEADS.items():
+            for (kind, Lq, Lk, ws, causal, groups), cell in zip(ROUTE_GEOMS.values(), rows[hd]):
+                for backward, tok in enumerate(cell.split("/")):
+                    calls.append((kind, Lq, Lk, C, nh, ws, causal, groups, backward, 1))
+                    f = fam[tok.rstrip("+")]
+                    want.append([ATTN_FAMILIES.index(f), *(ROUTE_PAIRS[hd] if f[0] == "a" else (0, 0)), int(tok.endswith("+"))])
+        job.append((env, calls))
+    assert set(ATTN_MODES) < set(ROUTE_ENVS) and len(want) == 6 * 7 * 10 * 2
+    # default mode, win4 at hd 66 with a tensor off the 16-byte grid: first generation both ways; t20 causal with 2^18 pixels at C = 528 (20 * 2^18 *
+    # 528 >= 2^31 elements): the 32-bit row offsets of attn_mfma do not reach, generic vector kernels
+    job.append(({}, [(0, 16, 16, 528, 8, 4, 0, 12, b, 0) for b in (0, 1)] + [(1, 20, 20, 528, 8, 0, 1, 1 << 18, b, 1) for b in (0, 1)]))
+    want += [[2, 3, 5, 1], [2, 3, 5, 1], [0, 0, 0, 0], [0, 0, 0, 0]]
+    assert 20 * (1 << 18) * 528 >= 1 << 31
+    r = subprocess.run([sys.executable, "-c", _ROUTE_CHILD, json.dumps(job)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    flat = [(m, c) for (_, calls), m in zip(job, list(ROUTE_ENVS) + ["extra"]) for c in calls]
+    bad = [(m, c, g, w) for (m, c), g, w in zip(flat, got, want) if g != w]
+    assert len(got) == len(want) and not bad, bad[:8]
+
+
 def test_graft_entry_build_runs():
     """the driver's build check (`__graft_entry__.build()`): compiles what changed, imports the package, checks the ABI version"""
     import importlib
@@ -917,6 +1001,19 @@ def test_attn_head_dims_cover_every_class():
     assert {attn_head_classes(hd)[0] for hd in hds} == reach_plain and {attn_head_classes(hd)[1] for hd in hds} == reach_gen2
     assert attn_head_classes(94) == ((3, 6), (3, 6)) and attn_head_classes(66) == ((3, 5), (3, 5)) and attn_head_classes(30) == ((1, 2), (1, 2))
     assert attn_head_classes(14) == ((1, 1), (1, 1)) and attn_head_classes(62) == ((2, 4), (2, 4)) and attn_head_classes(46) == ((2, 3), (2, 3))
+    # the library's own ladder (vptr_attn_route, T = 5 with nh = 2: C % 4 == 0): first generation under VPTR_ATTN16=2, second in the default routing
+    from helpers import attn_kernel_mode, attn_route
+    for hd in range(2, 97, 2):
+        with attn_kernel_mode("attn16"):
+            assert attn_route(1, 5, 5, 2 * hd, 2) == ("a16_gen1", attn_head_classes(hd)[0], 0), hd
+        with attn_kernel_mode("mfma"):
+            assert attn_route(1, 5, 5, 2 * hd, 2) == ("am_plain", attn_head_classes(hd)[0], 0), hd
+        with attn_kernel_mode("default"):
+            assert attn_route(1, 5, 5, 2 * hd, 2) == ("a16_gen2", attn_head_classes(hd)[1], 0), hd
+            assert attn_route(1, 5, 5, 2 * hd, 2, backward=1) == ("a16_gen2", attn_head_classes(hd)[1], 0), hd
+    for mode in ("default", "attn16", "mfma"):               # hd 98: refused by both matrix-unit families
+        with attn_kernel_mode(mode):
+            assert attn_route(1, 5, 5, 196, 2)[:2] == ("vector16", (0, 0)) and attn_route(1, 20, 20, 196, 2)[:2] == ("vector", (0, 0))
 
 
 def _emu():
@@ -947,8 +1044,8 @@ def test_attn_abi_dropout_conditions_hold_for_the_oracle(geom):
 
 
 def test_attn_abi_contract_cases_against_emulation():
-    """table-gradient accumulation, NULL table gradient, the workspace entry point (on the 65-window geometry), TSLMA with P16 outputs, the
-    nh = 3 slot-tail cases and the argument guards, emulated"""
+    """table-gradient accumulation, NULL table gradient, the workspace entry point (on the 65-window geometry), TSLMA with P16 outputs, the two
+    cases on tensors 8 bytes off the 16-byte grid, the nh = 3 slot-tail cases and the argument guards, emulated"""
     import attn_abi_cases as A
     from helpers import TS_GEOMS
     be = _emu()
@@ -956,6 +1053,8 @@ def test_attn_abi_contract_cases_against_emulation():
         A.run_table_contract(be, g, 2, 48)
     A.run_workspace_contract(be, A.LAUNCH_CASES["win4_65win_wpb2_tail"][0], 2, 48)
     A.run_tslma(be, *TS_GEOMS[1])
+    A.run_unaligned(be, A.GEOMS["win4_B3_8x8_bias"], 2, 48)
+    A.run_unaligned(be, A.GEOMS["t5x5_causal"], 8, 528)
     for name in ("mfma_win4_15prob_4slots", "mfma_t20_15prob_2slots", "mfma_t40_9prob_1slot", "win4_65win_wpb2_tail"):
         geom, hcs, _ = A.LAUNCH_CASES[name]
         A.run_parity(be, geom, *hcs[0])
@@ -981,6 +1080,49 @@ def test_attn_abi_case_geometries():
         return (q + 1 if q % 2 == 0 else q) * 4
     assert att_pitch(66) == 68 and 11 * att_pitch(66) // 2 <= 384 < 12 * att_pitch(66) // 2 and 16 * att_pitch(66) // 2 > 384
     assert P["mfma_win4_15prob_4slots"] * 3 % 4 != 0 and P["mfma_t20_15prob_2slots"] * 3 % 2 != 0
+    # the library's own split (vptr_attn_route, fp32 vector kernels, hd 66 at 1551 pixels): prefetching variant up to T = 11; not below 256 pixels
+    from helpers import ATTN_MODES, attn_geom_route, attn_kernel_mode, attn_route
+    with attn_kernel_mode("vector"):
+        for T in range(1, 17):
+            for backward in (0, 1):
+                assert attn_route(1, T, T, 132, 2, groups=1551, backward=backward) == ("vector16", (0, 0), int(T * att_pitch(66) // 2 <= 384)), T
+        assert attn_route(1, 11, 11, 132, 2, groups=1551)[2] == 1 and attn_route(1, 12, 11, 132, 2, groups=1551)[2] == 0
+        assert attn_route(1, 10, 10, 132, 2, groups=256)[2] == 1 and attn_route(1, 10, 10, 132, 2, groups=255)[2] == 0
+    # every id of the GPU file reaches, in its mode, the family that the id, the mode (helpers.attn_kernel_mode) and head_modes promise
+    A16, AM, VEC = {"a16_gen1", "a16_gen2"}, {"am_plain", "am_shared"}, {"vector", "vector16"}
+
+    def promised(mode, geom, hd):
+        """(forward, backward) family; geometry ids: "generic" = no 16-token kernel, "2qblocks" / "tileshare" = more than one query block"""
+        Lq, Lk = (geom[4] ** 2, geom[4] ** 2) if geom[0] == "win" else geom[2:4]
+        rows = max(Lq, Lk)
+        small = rows <= 16 and (geom[0] == "t" or geom[4] == 4)          # what the 16-token kernels (attn16.hip, vector) take
+        vec = "vector16" if small and (geom[0] == "t" or hd <= 92) else "vector"
+        am = ("am_plain", "am_shared" if Lq > 16 else "am_plain")
+        if hd > 96 or mode == "vector":
+            return vec, vec
+        if mode == "mfma" or rows > 16:
+            return am
+        if not small:
+            return "vector", "vector"
+        return {"default": ("a16_gen2", "a16_gen2"), "attn16": ("a16_gen1", "a16_gen1"), "attn16fwd": ("a16_gen1", vec)}[mode]
+    cases = [(A.GEOMS[g], nh, C, m, g + " " + hc) for hc, (nh, C) in A.HEAD_CLASSES.items() for g in A.GEOMS for m in A.head_modes(hc, ATTN_MODES)]
+    cases += [(g, nh, C, m, name) for name, (g, hcs, modes) in A.LAUNCH_CASES.items() for nh, C in hcs for m in (modes or ATTN_MODES)]
+    for geom, nh, C, mode, name in cases:
+        assert C % 4 == 0
+        with attn_kernel_mode(mode):
+            got = attn_geom_route(geom, nh, C, 0), attn_geom_route(geom, nh, C, 1)
+        assert (got[0][0], got[1][0]) == promised(mode, geom, C // nh), (name, mode, got)
+        fams = {got[0][0], got[1][0]}
+        if "over_limit_vector" in name or "generic" in name and mode != "mfma":
+            assert fams <= VEC and ("generic" not in name or fams == {"vector"}), (name, mode, got)
+        if name.startswith("mfma_") or ("2qblocks" in name or "tileshare" in name) and mode != "vector" and "over_limit" not in name:
+            assert fams <= AM and got[1][0] == ("am_plain" if "4slots" in name else "am_shared"), (name, mode, got)
+        if "_pf" in name and mode in ("vector", "attn16fwd"):        # the backward runs the 16-token temporal vector kernels in both modes
+            assert got[1][0] == "vector16" and got[1][2] == int("no_pf" not in name), (name, mode, got)
+        if name.startswith("win4_1547win") and mode == "default":
+            assert fams == {"a16_gen2"}
+        if name.startswith("win4_65win"):
+            assert mode == "vector" and fams == {"vector16"}
 
 
 def test_winattn16_register_tile_covers_the_lds_tile():
@@ -1000,6 +1142,12 @@ def test_winattn16_register_tile_covers_the_lds_tile():
         assert whole == (16 * h2 <= 768) == (hd <= 92), hd
     missing = {(l, d) for l in range(16) for d in range(50)} - staged(96)
     assert missing == {(15, d) for d in range(18, 50)}
+    # the library's own limit (vptr_attn_route): 4 x 4 windows on the fp32 vector kernels take the 16-token ones up to hd 92, forward and backward
+    from helpers import attn_kernel_mode, attn_route
+    with attn_kernel_mode("vector"):
+        for hd in range(2, 130, 2):
+            for backward in (0, 1):
+                assert attn_route(0, 16, 16, 2 * hd, 2, ws=4, groups=12, backward=backward)[0] == ("vector16" if hd <= 92 else "vector"), hd
 
 
 # ---- the conv-FFN forward kernels through the C ABI (tests/test_09c_convffn_fwd_gpu.py): reference builders, launch classes, the one-pass

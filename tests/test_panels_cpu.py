@@ -207,7 +207,7 @@ def test_feature_is_present():
     from vptr_amd.build import SOURCES
     assert "panels.hip" in SOURCES
     assert "vptr_clip_panels" in _lib.SIGNATURES and "vptr_clip_panels" in _lib.EXPORTS
-    assert len(_lib.SIGNATURES["vptr_clip_panels"]) == 18 and len(_lib.EXPORTS) == 76
+    assert len(_lib.SIGNATURES["vptr_clip_panels"]) == 18 and len(_lib.EXPORTS) == 77
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "vptr_clip_panels")
     with open(os.path.join(ROOT, "include", "vptr_hip.h")) as f:
         assert re.search(r"\bint\s+vptr_clip_panels\s*\(", f.read())

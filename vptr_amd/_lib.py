@@ -84,6 +84,7 @@ SIGNATURES = {
     "vptr_winattn_bwd_workspace": [I],
     "vptr_tattn_fwd": [P, P, P, P, I, I, I, I, I, I, I, F, P, U, I, P],
     "vptr_tattn_bwd": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P, U, F, I, P],
+    "vptr_attn_route": [I, I, I, I, I, I, I, L, I, I, P, I],   # host-side query: no stream
     "vptr_tattn_step": [P, P, P, P, I, I, I, I, I, I, P],
     "vptr_tsattn_fwd": [P, P, P, P, I, I, I, I, I, I, I, I, F, P, U, I, P],
     "vptr_tsattn_bwd": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, P, U, I, P],

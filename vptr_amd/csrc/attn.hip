@@ -2,6 +2,8 @@
 // per-pixel temporal attention.  Problems are tiny (16x16 or 64x64 windows, T<=50 time steps, head_dim 66), i.e.
 // 0.4 % of the model FLOPs, so they run in exact fp32 on the vector ALUs with every tile staged once through LDS;
 // the window partition / (T, N*HW, C) permutes of the reference are pure index arithmetic here.
+#include <initializer_list>
+
 #include "attn_mfma.h"
 
 #define ATT_MAXL 64   // max tokens per window (ws <= 8)
@@ -85,11 +87,6 @@ __global__ __launch_bounds__(256) void winattn_fwd_kernel(const float* __restric
 // 16-byte-aligned pitch of an ODD number of float4 (68 floats for head dim 66, zero padded), which makes the 16 row reads
 // of a score dot product conflict-free ds_read_b128 -- the first versions of these kernels were bound by ds_read_b32 count.
 // ------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ int att_pitch(int hd) {
-  int q = (hd + 3) / 4;
-  if ((q & 1) == 0) ++q;
-  return q * 4;
-}
 __device__ __forceinline__ float row16_sum(float v) {
   v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
   return v;
@@ -118,9 +115,6 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ src, float*
 struct Rows16 {
   float2 v[3];  // items tid, tid + 256, tid + 512 of the 16 x (hp / 2) float2 tile
 };
-// the three items per thread cover a tile of at most 768 float2: pitch <= 96, i.e. head dims up to 92; wider heads (94 .. : pitch 100, the
-// last row's columns 36 .. 99 would never be staged) take the generic window kernels
-static bool rows16_fits(int hd) { return 16 * (att_pitch(hd) / 2) <= 3 * 256; }
 __device__ __forceinline__ void rows16_load(Rows16& r, const float* __restrict__ src, int win, int H, int W, int C, int nqh, int nqw,
                                             int hoff, int hd, int hp, int tid) {
   const int h2 = hp >> 1, v2 = hd >> 1;
@@ -297,6 +291,34 @@ __global__ __launch_bounds__(256) void winattn16_bwd_kernel(const float* __restr
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// host side: every entry point checks its arguments, asks attn_route (attn_route.h) which family serves the call and launches that
+// ------------------------------------------------------------------------------------------------------------
+struct AttnGeoms {   // one problem set as attn_mfma.hip and attn16.hip describe it
+  AmGeom am;
+  A16Geom a16;
+};
+static AttnGeoms win_geoms(int B, int H, int W, int C, int nh, int ws) {
+  const int L = ws * ws, hd = C / nh, nwin = B * (H / ws) * (W / ws);
+  return {{0, H, W, ws, 0, 0, 0, L, L, C, nh, hd, nwin}, {0, H, W, 0, 0, 0, C, nh, hd, L, L, nwin, 0}};
+}
+static AttnGeoms t_geoms(int Nb, int Tq, int Tk, int HW, int C, int nh, int causal) {
+  const int hd = C / nh;
+  return {{1, 0, 0, 0, Tq, Tk, HW, Tq, Tk, C, nh, hd, Nb * HW}, {1, 0, 0, Tq, Tk, HW, C, nh, hd, Tq, Tk, Nb * HW, causal}};
+}
+static int attn_aligned16(std::initializer_list<const void*> tensors) {
+  uintptr_t bits = 0;
+  for (const void* t : tensors) bits |= reinterpret_cast<uintptr_t>(t);
+  return (bits & 15) == 0;
+}
+
+extern "C" int vptr_attn_route(int kind, int Lq, int Lk, int C, int nh, int ws, int causal, int64_t groups, int backward, int aligned16, int* out_host,
+                               int n) {
+  VPTR_CHECK(attn_route_query(kind, Lq, Lk, C, nh, ws, causal, groups, backward, aligned16, out_host, n) == 0,
+             "attn_route: n must be 1 .. 4 (got %d), out_host non-null, C and nh positive", n);
+  return 0;
+}
+
 extern "C" int vptr_winattn_fwd(const float* q, const float* k, const float* v, const float* bias_table,
                                 const int64_t* rel_index, float* o, int B, int H, int W, int C, int nh, int ws,
                                 float dropout_p, const uint64_t* seed_dev, uint32_t site, int p16, vptr_stream_t stream) {
@@ -307,37 +329,34 @@ extern "C" int vptr_winattn_fwd(const float* q, const float* k, const float* v, 
   VPTR_CHECK(ws * ws <= ATT_MAXL, "winattn_fwd: window too large (ws*ws <= %d)", ATT_MAXL);
   if (bias_table) VPTR_CHECK(rel_index != nullptr, "winattn_fwd: bias table needs rel_index");
   if (dropout_p > 0.f) VPTR_CHECK(seed_dev && dropout_p < 1.f, "winattn_fwd: dropout needs seed_dev");
-  const int L = ws * ws, hd = C / nh;
-  if (vptr_attn_mfma_ok(L, L, C, nh, 0, (int64_t)B * (H / ws) * (W / ws))) {
-    AmGeom gm = {0, H, W, ws, 0, 0, 0, L, L, C, nh, hd, B * (H / ws) * (W / ws)};
-    const int rc = vptr_attn_mfma_fwd(q, k, v, bias_table, rel_index, o, gm, 0, dropout_p, seed_dev, site, p16, (hipStream_t)stream);
-    if (rc) return rc;
-    VPTR_LAUNCH_CHECK();
-    return 0;
+  const int L = ws * ws, hd = C / nh, nwin = B * (H / ws) * (W / ws);
+  const hipStream_t st = (hipStream_t)stream;
+  const AttnGeoms g = win_geoms(B, H, W, C, nh, ws);
+  const AttnRoute r = attn_route(attn_mode_from_env(), 0, L, L, C, nh, ws, 0, (int64_t)B * (H / ws) * (W / ws), 0, attn_aligned16({q, k, v, o}));
+  int rc = 0;
+  switch (r.family) {
+    case VPTR_ATTN_FAMILY_AM_PLAIN:
+      rc = vptr_attn_mfma_fwd(q, k, v, bias_table, rel_index, o, g.am, r, 0, dropout_p, seed_dev, site, p16, st);
+      break;
+    case VPTR_ATTN_FAMILY_A16_GEN1:
+    case VPTR_ATTN_FAMILY_A16_GEN2:
+      rc = vptr_attn16_fwd(q, k, v, bias_table, rel_index, o, g.a16, r, dropout_p, seed_dev, site, p16, st);
+      break;
+    case VPTR_ATTN_FAMILY_VECTOR16: {
+      const int wpb = nwin >= 64 ? 2 : 1;   // two windows per workgroup: the second one's loads overlap the first one's math
+      const size_t lds16 = sizeof(float) * (3 * 16 * att_pitch(hd) + 16 * 20);
+      winattn16_fwd_kernel<<<dim3(cdiv(nwin, wpb), nh), 256, lds16, st>>>(q, k, v, bias_table, rel_index, o, nwin, H, W, C, nh, dropout_p, seed_dev, site,
+                                                                          wpb, p16);
+      break;
+    }
+    default: {
+      const size_t lds = sizeof(float) * (3 * L * (hd + 1) + L * (L + 1));
+      VPTR_CHECK(lds <= 160 * 1024, "winattn_fwd: LDS budget exceeded (%zu B)", lds);
+      if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)winattn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      winattn_fwd_kernel<<<dim3(nwin, nh), 256, lds, st>>>(q, k, v, bias_table, rel_index, o, H, W, C, nh, ws, dropout_p, seed_dev, site, p16);
+    }
   }
-  if (vptr_attn16_ok(0, L, L, C, nh, ws, 0)) {   // 4 x 4 windows: LDS-free MFMA kernels (attn16.hip)
-    A16Geom g16 = {0, H, W, 0, 0, 0, C, nh, hd, 16, 16, B * (H / 4) * (W / 4), 0};
-    const int rc = vptr_attn16_fwd(q, k, v, bias_table, rel_index, o, g16, dropout_p, seed_dev, site, p16, (hipStream_t)stream);
-    if (rc) return rc;
-    VPTR_LAUNCH_CHECK();
-    return 0;
-  }
-  if (ws == 4 && hd % 2 == 0 && C % 2 == 0 && rows16_fits(hd)) {
-    const int nwin = B * (H / 4) * (W / 4);
-    const int wpb = nwin >= 64 ? 2 : 1;   // two windows per workgroup: the second one's loads overlap the first one's math
-    const size_t lds16 = sizeof(float) * (3 * 16 * att_pitch(hd) + 16 * 20);
-    winattn16_fwd_kernel<<<dim3(cdiv(nwin, wpb), nh), 256, lds16, (hipStream_t)stream>>>(q, k, v, bias_table, rel_index, o, nwin, H, W, C,
-                                                                                         nh, dropout_p, seed_dev, site, wpb, p16);
-    VPTR_LAUNCH_CHECK();
-    return 0;
-  }
-  const size_t lds = sizeof(float) * (3 * L * (hd + 1) + L * (L + 1));
-  VPTR_CHECK(lds <= 160 * 1024, "winattn_fwd: LDS budget exceeded (%zu B)", lds);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)winattn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  dim3 grid(B * (H / ws) * (W / ws), nh);
-  winattn_fwd_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(q, k, v, bias_table, rel_index, o, H, W, C, nh, ws, dropout_p,
-                                                             seed_dev, site, p16);
+  if (rc) return rc;
   VPTR_LAUNCH_CHECK();
   return 0;
 }
@@ -461,41 +480,40 @@ extern "C" int vptr_winattn_bwd_ws(const float* q, const float* k, const float* 
   if (dropout_p > 0.f) VPTR_CHECK(seed_dev && dropout_p < 1.f, "winattn_bwd: dropout needs seed_dev");
   const int L = ws * ws, hd = C / nh, ntab = (2 * ws - 1) * (2 * ws - 1);
   const int nwin = B * (H / ws) * (W / ws);
-  if (vptr_attn_mfma_ok(L, L, C, nh, 0, (int64_t)B * (H / ws) * (W / ws))) {
-    AmGeom gm = {0, H, W, ws, 0, 0, 0, L, L, C, nh, hd, nwin};
-    const int rc = vptr_attn_mfma_bwd(q, k, v, bias_table, rel_index, dout, dq, dk, dv, dbias_table, gm, 0, dropout_p, seed_dev, site, dq_scale, p16,
-                                      (hipStream_t)stream);
-    if (rc) return rc;
-    VPTR_LAUNCH_CHECK();
-    return 0;
+  const hipStream_t st = (hipStream_t)stream;
+  const AttnGeoms g = win_geoms(B, H, W, C, nh, ws);
+  const AttnRoute r = attn_route(attn_mode_from_env(), 0, L, L, C, nh, ws, 0, (int64_t)B * (H / ws) * (W / ws), 1,
+                                 attn_aligned16({q, k, v, dout, dq, dk, dv}));
+  int rc = 0;
+  switch (r.family) {
+    case VPTR_ATTN_FAMILY_AM_PLAIN:
+    case VPTR_ATTN_FAMILY_AM_SHARED:
+      rc = vptr_attn_mfma_bwd(q, k, v, bias_table, rel_index, dout, dq, dk, dv, dbias_table, g.am, r, 0, dropout_p, seed_dev, site, dq_scale, p16, st);
+      break;
+    case VPTR_ATTN_FAMILY_A16_GEN1:
+    case VPTR_ATTN_FAMILY_A16_GEN2:
+      rc = vptr_attn16_bwd(q, k, v, bias_table, rel_index, dout, dq, dk, dv, dbias_table, g.a16, r, dropout_p, seed_dev, site, dq_scale, p16, workspace,
+                           workspace_floats, st);
+      break;
+    case VPTR_ATTN_FAMILY_VECTOR16: {
+      // many windows per workgroup: the 49 bias-table atomics per workgroup hit the same 49*nh addresses from every workgroup
+      // with a bias-table gradient, fewer and longer workgroups (their 49 atomics per head all hit the same 392 words)
+      const int wpb16 = nwin >= 512 ? (dbias_table ? 8 : 4) : (nwin >= 64 ? 2 : 1);
+      const size_t lds16 = sizeof(float) * (4 * 16 * att_pitch(hd) + 2 * 16 * 20);
+      winattn16_bwd_kernel<<<dim3(cdiv(nwin, wpb16), nh), 256, lds16, st>>>(q, k, v, bias_table, rel_index, dout, dq, dk, dv, dbias_table, nwin, H, W, C, nh,
+                                                                            dropout_p, seed_dev, site, wpb16, dq_scale, p16);
+      break;
+    }
+    default: {
+      const size_t lds = sizeof(float) * (4 * L * (hd + 1) + 2 * L * (L + 1) + ntab);
+      VPTR_CHECK(lds <= 160 * 1024, "winattn_bwd: LDS budget exceeded (%zu B)", lds);
+      const int wpb = nwin >= 2048 ? 4 : 1;
+      if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)winattn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      winattn_bwd_kernel<<<dim3(cdiv(nwin, wpb), nh), 256, lds, st>>>(q, k, v, bias_table, rel_index, dout, dq, dk, dv, dbias_table, nwin, H, W, C, nh, ws,
+                                                                      dropout_p, seed_dev, site, wpb, dq_scale, p16);
+    }
   }
-  if (vptr_attn16_ok(0, L, L, C, nh, ws, 1)) {
-    A16Geom g16 = {0, H, W, 0, 0, 0, C, nh, hd, 16, 16, nwin, 0};
-    const int rc = vptr_attn16_bwd(q, k, v, bias_table, rel_index, dout, dq, dk, dv, dbias_table, g16, dropout_p, seed_dev, site, dq_scale, p16,
-                                   workspace, workspace_floats, (hipStream_t)stream);
-    if (rc) return rc;
-    VPTR_LAUNCH_CHECK();
-    return 0;
-  }
-  if (ws == 4 && hd % 2 == 0 && C % 2 == 0 && rows16_fits(hd)) {
-    // many windows per workgroup: the 49 bias-table atomics per workgroup hit the same 49*nh addresses from every workgroup
-    // with a bias-table gradient, fewer and longer workgroups (their 49 atomics per head all hit the same 392 words)
-    const int wpb16 = nwin >= 512 ? (dbias_table ? 8 : 4) : (nwin >= 64 ? 2 : 1);
-    const size_t lds16 = sizeof(float) * (4 * 16 * att_pitch(hd) + 2 * 16 * 20);
-    winattn16_bwd_kernel<<<dim3(cdiv(nwin, wpb16), nh), 256, lds16, (hipStream_t)stream>>>(q, k, v, bias_table, rel_index, dout, dq, dk,
-                                                                                          dv, dbias_table, nwin, H, W, C, nh,
-                                                                                          dropout_p, seed_dev, site, wpb16, dq_scale, p16);
-    VPTR_LAUNCH_CHECK();
-    return 0;
-  }
-  const size_t lds = sizeof(float) * (4 * L * (hd + 1) + 2 * L * (L + 1) + ntab);
-  VPTR_CHECK(lds <= 160 * 1024, "winattn_bwd: LDS budget exceeded (%zu B)", lds);
-  const int wpb = nwin >= 2048 ? 4 : 1;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)winattn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  winattn_bwd_kernel<<<dim3(cdiv(nwin, wpb), nh), 256, lds, (hipStream_t)stream>>>(q, k, v, bias_table, rel_index, dout, dq, dk, dv,
-                                                                                 dbias_table, nwin, H, W, C, nh, ws, dropout_p,
-                                                                                 seed_dev, site, wpb, dq_scale, p16);
+  if (rc) return rc;
   VPTR_LAUNCH_CHECK();
   return 0;
 }
@@ -563,8 +581,6 @@ __global__ __launch_bounds__(64) void tattn_fwd_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------------------------------
 // Temporal fast path, register-staged rows: T x (hp / 2) float2 items over one wave, at most TR_NIT per lane (T = 10,
 // head dim 66: 340 items = 6 per lane).  Used to fetch the NEXT pixel's rows while the current pixel is computed.
-#define TR_NIT 6
-#define TR_PPW 4   // consecutive pixels per wave in the prefetching variant
 struct TRows {
   float2 v[TR_NIT];
 };
@@ -768,36 +784,35 @@ extern "C" int vptr_tattn_fwd(const float* q, const float* k, const float* v, fl
   if (causal) VPTR_CHECK(Tq == Tk, "tattn_fwd: causal mask needs Tq == Tk");
   if (dropout_p > 0.f) VPTR_CHECK(seed_dev && dropout_p < 1.f, "tattn_fwd: dropout needs seed_dev");
   const int hd = C / nh;
-  if (vptr_attn_mfma_ok(Tq, Tk, C, nh, causal, (int64_t)Nb * HW)) {
-    AmGeom gm = {1, 0, 0, 0, Tq, Tk, HW, Tq, Tk, C, nh, hd, Nb * HW};
-    const int rc = vptr_attn_mfma_fwd(q, k, v, nullptr, nullptr, o, gm, causal, dropout_p, seed_dev, site, p16, (hipStream_t)stream);
-    if (rc) return rc;
-    VPTR_LAUNCH_CHECK();
-    return 0;
+  const hipStream_t st = (hipStream_t)stream;
+  const AttnGeoms g = t_geoms(Nb, Tq, Tk, HW, C, nh, causal);
+  const AttnRoute r = attn_route(attn_mode_from_env(), 1, Tq, Tk, C, nh, 0, causal, (int64_t)Nb * HW, 0, attn_aligned16({q, k, v, o}));
+  int rc = 0;
+  switch (r.family) {
+    case VPTR_ATTN_FAMILY_AM_PLAIN:
+      rc = vptr_attn_mfma_fwd(q, k, v, nullptr, nullptr, o, g.am, r, causal, dropout_p, seed_dev, site, p16, st);
+      break;
+    case VPTR_ATTN_FAMILY_A16_GEN1:
+    case VPTR_ATTN_FAMILY_A16_GEN2:
+      rc = vptr_attn16_fwd(q, k, v, nullptr, nullptr, o, g.a16, r, dropout_p, seed_dev, site, p16, st);
+      break;
+    case VPTR_ATTN_FAMILY_VECTOR16: {
+      const size_t lds16 = sizeof(float) * ((Tq + 2 * Tk) * att_pitch(hd) + 16 * 20);
+      if (r.variant)
+        tattn16_fwd_kernel<true><<<dim3(cdiv(cdiv(Nb * HW, TR_PPW), 8) * 8 * nh), 64, lds16, st>>>(q, k, v, o, Tq, Tk, HW, C, nh, causal, dropout_p, seed_dev,
+                                                                                                   site, Nb * HW, p16);
+      else
+        tattn16_fwd_kernel<false><<<dim3(cdiv(Nb * HW, 8) * 8 * nh), 64, lds16, st>>>(q, k, v, o, Tq, Tk, HW, C, nh, causal, dropout_p, seed_dev, site, Nb * HW,
+                                                                                      p16);
+      break;
+    }
+    default: {
+      const size_t lds = sizeof(float) * ((Tq + 2 * Tk) * (hd + 1) + Tq * (Tk + 1));
+      VPTR_CHECK(lds <= 64 * 1024, "tattn_fwd: LDS budget exceeded (%zu B)", lds);
+      tattn_fwd_kernel<<<dim3(Nb * HW, nh), 64, lds, st>>>(q, k, v, o, Tq, Tk, HW, C, nh, causal, dropout_p, seed_dev, site, p16);
+    }
   }
-  if (vptr_attn16_ok(1, Tq, Tk, C, nh, 0, 0)) {   // T <= 16: LDS-free MFMA kernels (attn16.hip)
-    A16Geom g16 = {1, 0, 0, Tq, Tk, HW, C, nh, hd, Tq, Tk, Nb * HW, causal};
-    const int rc = vptr_attn16_fwd(q, k, v, nullptr, nullptr, o, g16, dropout_p, seed_dev, site, p16, (hipStream_t)stream);
-    if (rc) return rc;
-    VPTR_LAUNCH_CHECK();
-    return 0;
-  }
-  if (Tq <= 16 && Tk <= 16 && hd % 2 == 0 && C % 2 == 0) {
-    const size_t lds16 = sizeof(float) * ((Tq + 2 * Tk) * att_pitch(hd) + 16 * 20);
-    const int items = (Tq > Tk ? Tq : Tk) * (att_pitch(hd) / 2);
-    if (items <= 64 * TR_NIT && Nb * HW >= 64 * TR_PPW)
-      tattn16_fwd_kernel<true><<<dim3(cdiv(cdiv(Nb * HW, TR_PPW), 8) * 8 * nh), 64, lds16, (hipStream_t)stream>>>(
-          q, k, v, o, Tq, Tk, HW, C, nh, causal, dropout_p, seed_dev, site, Nb * HW, p16);
-    else
-      tattn16_fwd_kernel<false><<<dim3(cdiv(Nb * HW, 8) * 8 * nh), 64, lds16, (hipStream_t)stream>>>(q, k, v, o, Tq, Tk, HW, C, nh, causal,
-                                                                                                    dropout_p, seed_dev, site, Nb * HW, p16);
-    VPTR_LAUNCH_CHECK();
-    return 0;
-  }
-  const size_t lds = sizeof(float) * ((Tq + 2 * Tk) * (hd + 1) + Tq * (Tk + 1));
-  VPTR_CHECK(lds <= 64 * 1024, "tattn_fwd: LDS budget exceeded (%zu B)", lds);
-  tattn_fwd_kernel<<<dim3(Nb * HW, nh), 64, lds, (hipStream_t)stream>>>(q, k, v, o, Tq, Tk, HW, C, nh, causal, dropout_p, seed_dev,
-                                                                       site, p16);
+  if (rc) return rc;
   VPTR_LAUNCH_CHECK();
   return 0;
 }
@@ -980,40 +995,37 @@ extern "C" int vptr_tattn_bwd(const float* q, const float* k, const float* v, co
   if (causal) VPTR_CHECK(Tq == Tk, "tattn_bwd: causal mask needs Tq == Tk");
   if (dropout_p > 0.f) VPTR_CHECK(seed_dev && dropout_p < 1.f, "tattn_bwd: dropout needs seed_dev");
   const int hd = C / nh;
-  if (vptr_attn_mfma_ok(Tq, Tk, C, nh, causal, (int64_t)Nb * HW)) {
-    AmGeom gm = {1, 0, 0, 0, Tq, Tk, HW, Tq, Tk, C, nh, hd, Nb * HW};
-    const int rc = vptr_attn_mfma_bwd(q, k, v, nullptr, nullptr, dout, dq, dk, dv, nullptr, gm, causal, dropout_p, seed_dev, site, dq_scale, p16,
-                                      (hipStream_t)stream);
-    if (rc) return rc;
-    VPTR_LAUNCH_CHECK();
-    return 0;
+  const hipStream_t st = (hipStream_t)stream;
+  const AttnGeoms g = t_geoms(Nb, Tq, Tk, HW, C, nh, causal);
+  const AttnRoute r = attn_route(attn_mode_from_env(), 1, Tq, Tk, C, nh, 0, causal, (int64_t)Nb * HW, 1, attn_aligned16({q, k, v, dout, dq, dk, dv}));
+  int rc = 0;
+  switch (r.family) {
+    case VPTR_ATTN_FAMILY_AM_PLAIN:
+    case VPTR_ATTN_FAMILY_AM_SHARED:
+      rc = vptr_attn_mfma_bwd(q, k, v, nullptr, nullptr, dout, dq, dk, dv, nullptr, g.am, r, causal, dropout_p, seed_dev, site, dq_scale, p16, st);
+      break;
+    case VPTR_ATTN_FAMILY_A16_GEN1:
+    case VPTR_ATTN_FAMILY_A16_GEN2:
+      rc = vptr_attn16_bwd(q, k, v, nullptr, nullptr, dout, dq, dk, dv, nullptr, g.a16, r, dropout_p, seed_dev, site, dq_scale, p16, nullptr, 0, st);
+      break;
+    case VPTR_ATTN_FAMILY_VECTOR16: {
+      const size_t lds16 = sizeof(float) * (2 * (Tq + Tk) * att_pitch(hd) + 2 * 16 * 20);
+      if (r.variant)
+        tattn16_bwd_kernel<true><<<dim3(cdiv(cdiv(Nb * HW, TR_PPW), 8) * 8 * nh), 64, lds16, st>>>(q, k, v, dout, dq, dk, dv, Tq, Tk, HW, C, nh, causal, dropout_p,
+                                                                                                   seed_dev, site, Nb * HW, dq_scale, p16);
+      else
+        tattn16_bwd_kernel<false><<<dim3(cdiv(Nb * HW, 8) * 8 * nh), 64, lds16, st>>>(q, k, v, dout, dq, dk, dv, Tq, Tk, HW, C, nh, causal, dropout_p, seed_dev,
+                                                                                      site, Nb * HW, dq_scale, p16);
+      break;
+    }
+    default: {
+      const size_t lds = sizeof(float) * (2 * (Tq + Tk) * (hd + 1) + 2 * Tq * (Tk + 1));
+      VPTR_CHECK(lds <= 160 * 1024, "tattn_bwd: LDS budget exceeded (%zu B)", lds);
+      if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tattn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      tattn_bwd_kernel<<<dim3(Nb * HW, nh), 64, lds, st>>>(q, k, v, dout, dq, dk, dv, Tq, Tk, HW, C, nh, causal, dropout_p, seed_dev, site, dq_scale, p16);
+    }
   }
-  if (vptr_attn16_ok(1, Tq, Tk, C, nh, 0, 1)) {
-    A16Geom g16 = {1, 0, 0, Tq, Tk, HW, C, nh, hd, Tq, Tk, Nb * HW, causal};
-    const int rc = vptr_attn16_bwd(q, k, v, nullptr, nullptr, dout, dq, dk, dv, nullptr, g16, dropout_p, seed_dev, site, dq_scale, p16, nullptr, 0,
-                                   (hipStream_t)stream);
-    if (rc) return rc;
-    VPTR_LAUNCH_CHECK();
-    return 0;
-  }
-  if (Tq <= 16 && Tk <= 16 && hd % 2 == 0 && C % 2 == 0) {
-    const size_t lds16 = sizeof(float) * (2 * (Tq + Tk) * att_pitch(hd) + 2 * 16 * 20);
-    const int items = (Tq > Tk ? Tq : Tk) * (att_pitch(hd) / 2);
-    if (items <= 64 * TR_NIT && Nb * HW >= 64 * TR_PPW)
-      tattn16_bwd_kernel<true><<<dim3(cdiv(cdiv(Nb * HW, TR_PPW), 8) * 8 * nh), 64, lds16, (hipStream_t)stream>>>(
-          q, k, v, dout, dq, dk, dv, Tq, Tk, HW, C, nh, causal, dropout_p, seed_dev, site, Nb * HW, dq_scale, p16);
-    else
-      tattn16_bwd_kernel<false><<<dim3(cdiv(Nb * HW, 8) * 8 * nh), 64, lds16, (hipStream_t)stream>>>(
-          q, k, v, dout, dq, dk, dv, Tq, Tk, HW, C, nh, causal, dropout_p, seed_dev, site, Nb * HW, dq_scale, p16);
-    VPTR_LAUNCH_CHECK();
-    return 0;
-  }
-  const size_t lds = sizeof(float) * (2 * (Tq + Tk) * (hd + 1) + 2 * Tq * (Tk + 1));
-  VPTR_CHECK(lds <= 160 * 1024, "tattn_bwd: LDS budget exceeded (%zu B)", lds);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)tattn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  tattn_bwd_kernel<<<dim3(Nb * HW, nh), 64, lds, (hipStream_t)stream>>>(q, k, v, dout, dq, dk, dv, Tq, Tk, HW, C, nh, causal,
-                                                                       dropout_p, seed_dev, site, dq_scale, p16);
+  if (rc) return rc;
   VPTR_LAUNCH_CHECK();
   return 0;
 }

@@ -15,6 +15,8 @@
 // Every product is split-bf16 (x = hi + lo; lo*hi + hi*lo + hi*hi, fp32 accumulate): fp32-class accuracy like the GEMMs.  Dropout
 // masks hash the same element indices as the fp32 vector kernels of attn.hip (mask-exact parity test), the relative-position bias is
 // 4 registers per lane, its gradient is summed in registers over a wave's problems and leaves through 49 LDS words per workgroup.
+#include <type_traits>
+
 #include "attn_mfma.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
@@ -777,14 +779,8 @@ __global__ __launch_bounds__(1024) void attn16_dtable_reduce_kernel(const float*
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// host side (called by the entry points of attn.hip)
+// host side (called by the entry points of attn.hip with the route of attn_route.h)
 // ---------------------------------------------------------------------------------------------------------------------------
-static int a16_mode() {   // read per call (tests switch modes inside one process).  VPTR_ATTN16: 0 = off; 1 (default) = second-generation
-  const char* m = getenv("VPTR_ATTN_MFMA");   // forward and backward (C % 4 == 0 and 16-byte aligned tensors, else the first-generation
-  if (m && atoi(m) != 1) return 0;             // forward + the fp32 vector backward); 2 = first-generation forward and backward; 4 = first-
-  const char* e = getenv("VPTR_ATTN16");       // generation forward, vector backward.  VPTR_ATTN16_FWD1=1: mode 1 with the first-generation
-  return e ? atoi(e) : 1;                      // forward.  An explicit VPTR_ATTN_MFMA=0 / 2 (vector / LDS-staged MFMA kernels everywhere)
-}                                              // turns these kernels off
 // Measured at the K64 shapes (tools/attn_bench.py, P16 outputs, dropout 0.1; copying the bytes of a forward call: 19 us):
 //   forward,  first generation    24-25 us   (fp32 vector kernels 35-37)
 //   forward,  second generation   20 / 23 us (window / temporal)
@@ -792,13 +788,21 @@ static int a16_mode() {   // read per call (tests switch modes inside one proces
 //                                 narrow memory instructions per (problem, head), see above
 //   backward, second generation   49 / 47 us (window without a table gradient 42; with the table gradient through atomics instead of
 //                                 the workspace 81)
-bool vptr_attn16_ok(int kind, int Lq, int Lk, int C, int nh, int ws, int backward) {
-  const int hd = C / nh;
-  const int mode = a16_mode();
-  if (mode == 0 || (backward && mode == 4)) return false;
-  if (backward && mode == 1 && C % 4 != 0) return false;   // default: the second-generation backward, which needs 16-byte aligned rows
-  if (kind == 0 && ws != 4) return false;
-  return Lq >= 1 && Lk >= 1 && Lq <= 16 && Lk <= 16 && hd % 2 == 0 && C % 2 == 0 && hd <= 96;
+template <int V> using A16Int = std::integral_constant<int, V>;
+// launch(A, B, FULL) with the route's template pair and <FULL> variant as integral constants; <4, 7> exists in the second generation only
+template <bool GEN2, class F>
+static int a16_dispatch(const AttnRoute& r, F&& launch) {
+#define A16_CASE(A, B)                                      \
+  if (r.a == A && r.b == B) {                               \
+    if (r.variant) launch(A16Int<A>{}, A16Int<B>{}, std::true_type{});   \
+    else launch(A16Int<A>{}, A16Int<B>{}, std::false_type{});            \
+    return 0;                                               \
+  }
+  A16_CASE(1, 1) A16_CASE(1, 2) A16_CASE(2, 3) A16_CASE(2, 4) A16_CASE(3, 5) A16_CASE(3, 6)
+  if constexpr (GEN2) A16_CASE(4, 7)
+#undef A16_CASE
+  vptr_set_error("attn16: no instantiation <%d, %d>", r.a, r.b);
+  return -1;
 }
 static dim3 a16_grid(const A16Geom& g, const bool table_grad) {
   // 4-wave workgroups, 3 - 4 resident per CU, each looping over its share of the problems.  A few rounds of workgroups keep the tail
@@ -808,102 +812,54 @@ static dim3 a16_grid(const A16Geom& g, const bool table_grad) {
   const int want = (table_grad ? 256 * 2 : 256 * 4 * 3) / groups;
   return dim3(g.nprob < want ? g.nprob : want, groups);
 }
-static bool a16_full(const A16Geom& g) { return g.Lq == 16 && g.Lk == 16 && !g.causal; }
-int vptr_attn16_fwd(const float* q, const float* k, const float* v, const float* table, const int64_t* rel_index, float* o, const A16Geom& g, float p,
-                    const uint64_t* seed_dev, uint32_t site, int p16, hipStream_t st) {
-  const bool full = a16_full(g);
-  const uintptr_t fbits = reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(o);
-  if (a16_mode() == 1 && g.C % 4 == 0 && (fbits & 15) == 0 && !getenv("VPTR_ATTN16_FWD1")) {   // second generation
-    const int span = g.hd + ((g.hd & 3) ? 2 : 0);
-    const int nb32 = (span + 31) / 32, nb16 = (span + 15) / 16;
+// second generation: `per_cu` workgroups per CU and head group, each with the next problem's loads in flight
+static dim3 a16_grid2(const A16Geom& g, const int per_cu) {
+  const int groups = (g.nh + 3) / 4;
+  int gx = 256 * per_cu / groups;
+  if (gx < 1) gx = 1;
+  if (g.nprob < gx) gx = g.nprob;
+  return dim3(gx, groups);
+}
+int vptr_attn16_fwd(const float* q, const float* k, const float* v, const float* table, const int64_t* rel_index, float* o, const A16Geom& g,
+                    const AttnRoute& r, float p, const uint64_t* seed_dev, uint32_t site, int p16, hipStream_t st) {
+  if (r.family == VPTR_ATTN_FAMILY_A16_GEN2) {
     const int rows = ((g.Lq > g.Lk ? g.Lq : g.Lk) + 3) & ~3;
-    const int groups = (g.nh + 3) / 4;
-    const size_t lds = (size_t)4 * 2 * rows * nb16 * 32;
-    int gx = 256 * 3 / groups;
-    if (gx < 1) gx = 1;
-    if (g.nprob < gx) gx = g.nprob;
-    const dim3 grid(gx, groups), block(256);
-#define A16F2(A, B)                                                                                                                  \
-  do {                                                                                                                               \
-    if (full) attn16_fwd2_kernel<A, B, true><<<grid, block, lds, st>>>(q, k, v, table, rel_index, o, g, p, seed_dev, site, p16, rows);   \
-    else attn16_fwd2_kernel<A, B, false><<<grid, block, lds, st>>>(q, k, v, table, rel_index, o, g, p, seed_dev, site, p16, rows);       \
-  } while (0)
-    if (nb32 == 1 && nb16 == 1) A16F2(1, 1);
-    else if (nb32 == 1) A16F2(1, 2);
-    else if (nb32 == 2 && nb16 == 3) A16F2(2, 3);
-    else if (nb32 == 2) A16F2(2, 4);
-    else if (nb16 == 5) A16F2(3, 5);
-    else if (nb32 == 3) A16F2(3, 6);
-    else A16F2(4, 7);
-#undef A16F2
-    return 0;
+    const size_t lds = (size_t)4 * 2 * rows * r.b * 32;
+    const dim3 grid = a16_grid2(g, 3);
+    return a16_dispatch<true>(r, [&](auto A, auto B, auto F) {
+      attn16_fwd2_kernel<decltype(A)::value, decltype(B)::value, decltype(F)::value><<<grid, 256, lds, st>>>(q, k, v, table, rel_index, o, g, p, seed_dev,
+                                                                                                             site, p16, rows);
+    });
   }
-  const int nb32 = (g.hd + 31) / 32, nb16 = (g.hd + 15) / 16;
-  const dim3 grid = a16_grid(g, false), block(256);
-#define A16F(A, B)                                                                                                        \
-  do {                                                                                                                    \
-    if (full) attn16_fwd_kernel<A, B, true><<<grid, block, 0, st>>>(q, k, v, table, rel_index, o, g, p, seed_dev, site, p16);   \
-    else attn16_fwd_kernel<A, B, false><<<grid, block, 0, st>>>(q, k, v, table, rel_index, o, g, p, seed_dev, site, p16);       \
-  } while (0)
-  if (nb32 == 1 && nb16 == 1) A16F(1, 1);
-  else if (nb32 == 1) A16F(1, 2);
-  else if (nb32 == 2 && nb16 == 3) A16F(2, 3);
-  else if (nb32 == 2) A16F(2, 4);
-  else if (nb16 == 5) A16F(3, 5);
-  else A16F(3, 6);
-#undef A16F
-  return 0;
+  const dim3 grid = a16_grid(g, false);
+  return a16_dispatch<false>(r, [&](auto A, auto B, auto F) {
+    attn16_fwd_kernel<decltype(A)::value, decltype(B)::value, decltype(F)::value><<<grid, 256, 0, st>>>(q, k, v, table, rel_index, o, g, p, seed_dev, site,
+                                                                                                        p16);
+  });
 }
 int vptr_attn16_bwd(const float* q, const float* k, const float* v, const float* table, const int64_t* rel_index, const float* dout, float* dq, float* dk,
-                    float* dv, float* dtable, const A16Geom& g, float p, const uint64_t* seed_dev, uint32_t site, float dq_scale, int p16,
-                    float* dtable_ws, int64_t ws_floats, hipStream_t st) {
-  const bool full = a16_full(g);
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(dout) |
-                         reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(dk) | reinterpret_cast<uintptr_t>(dv);
-  if (a16_mode() != 2 && g.C % 4 == 0 && (bits & 15) == 0) {   // second generation: aligned heads, LDS stash, prefetch
-    const int span = g.hd + ((g.hd & 3) ? 2 : 0);                // a head that starts on an odd pair begins 2 channels early
-    const int nb32 = (span + 31) / 32, nb16 = (span + 15) / 16;
+                    float* dv, float* dtable, const A16Geom& g, const AttnRoute& r, float p, const uint64_t* seed_dev, uint32_t site, float dq_scale,
+                    int p16, float* dtable_ws, int64_t ws_floats, hipStream_t st) {
+  if (r.family == VPTR_ATTN_FAMILY_A16_GEN2) {   // aligned heads, LDS stash, prefetch
     const int rows = ((g.Lq > g.Lk ? g.Lq : g.Lk) + 3) & ~3;
-    const int groups = (g.nh + 3) / 4;
-    const size_t lds = (size_t)4 * 6 * rows * nb16 * 32;
-    const int per_cu = 2;   // 219 - 224 registers: two workgroups (8 waves) per CU, each with the next problem's loads in flight
-    int gx = 256 * per_cu / groups;
-    if (gx < 1) gx = 1;
-    if (g.nprob < gx) gx = g.nprob;
+    const size_t lds = (size_t)4 * 6 * rows * r.b * 32;
+    const dim3 grid = a16_grid2(g, 2);   // 219 - 224 registers: two workgroups (8 waves) per CU
+    const int gx = grid.x, groups = grid.y;
     float* ws = nullptr;
     if (dtable && dtable_ws && ws_floats >= (int64_t)gx * groups * 4 * 52) ws = dtable_ws;
-    const dim3 grid(gx, groups), block(256);
-#define A16B2(A, B)                                                                                                                                \
-  do {                                                                                                                                             \
-    if (full) attn16_bwd2_kernel<A, B, true><<<grid, block, lds, st>>>(q, k, v, table, rel_index, dout, dq, dk, dv, dtable, ws, g, p, seed_dev, site, dq_scale, p16, rows);  \
-    else attn16_bwd2_kernel<A, B, false><<<grid, block, lds, st>>>(q, k, v, table, rel_index, dout, dq, dk, dv, dtable, ws, g, p, seed_dev, site, dq_scale, p16, rows);      \
-  } while (0)
-    if (nb32 == 1 && nb16 == 1) A16B2(1, 1);
-    else if (nb32 == 1) A16B2(1, 2);
-    else if (nb32 == 2 && nb16 == 3) A16B2(2, 3);
-    else if (nb32 == 2) A16B2(2, 4);
-    else if (nb16 == 5) A16B2(3, 5);
-    else if (nb32 == 3) A16B2(3, 6);
-    else A16B2(4, 7);
-#undef A16B2
-    if (ws) attn16_dtable_reduce_kernel<<<g.nh, 1024, 0, st>>>(ws, dtable, gx, groups * 4, g.nh);
-    return 0;
+    const int rc = a16_dispatch<true>(r, [&](auto A, auto B, auto F) {
+      attn16_bwd2_kernel<decltype(A)::value, decltype(B)::value, decltype(F)::value><<<grid, 256, lds, st>>>(q, k, v, table, rel_index, dout, dq, dk, dv,
+                                                                                                             dtable, ws, g, p, seed_dev, site, dq_scale,
+                                                                                                             p16, rows);
+    });
+    if (rc == 0 && ws) attn16_dtable_reduce_kernel<<<g.nh, 1024, 0, st>>>(ws, dtable, gx, groups * 4, g.nh);
+    return rc;
   }
-  const int nb32 = (g.hd + 31) / 32, nb16 = (g.hd + 15) / 16;
-  const dim3 grid = a16_grid(g, dtable != nullptr), block(256);
-#define A16B(A, B)                                                                                                                                                   \
-  do {                                                                                                                                                               \
-    if (full) attn16_bwd_kernel<A, B, true><<<grid, block, 0, st>>>(q, k, v, table, rel_index, dout, dq, dk, dv, dtable, g, p, seed_dev, site, dq_scale, p16);      \
-    else attn16_bwd_kernel<A, B, false><<<grid, block, 0, st>>>(q, k, v, table, rel_index, dout, dq, dk, dv, dtable, g, p, seed_dev, site, dq_scale, p16);          \
-  } while (0)
-  if (nb32 == 1 && nb16 == 1) A16B(1, 1);
-  else if (nb32 == 1) A16B(1, 2);
-  else if (nb32 == 2 && nb16 == 3) A16B(2, 3);
-  else if (nb32 == 2) A16B(2, 4);
-  else if (nb16 == 5) A16B(3, 5);
-  else A16B(3, 6);
-#undef A16B
-  return 0;
+  const dim3 grid = a16_grid(g, dtable != nullptr);
+  return a16_dispatch<false>(r, [&](auto A, auto B, auto F) {
+    attn16_bwd_kernel<decltype(A)::value, decltype(B)::value, decltype(F)::value><<<grid, 256, 0, st>>>(q, k, v, table, rel_index, dout, dq, dk, dv, dtable,
+                                                                                                        g, p, seed_dev, site, dq_scale, p16);
+  });
 }
 // floats of workspace that make the bias-table gradient of a backward call atomics-free (at most 3 workgroups per CU and head group)
 int64_t vptr_attn16_ws_floats(int nh) { (void)nh; return (int64_t)256 * 2 * 4 * 52; }

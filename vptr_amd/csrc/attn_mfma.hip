@@ -16,13 +16,13 @@
 //                bf16 hi / lo image [keys][16 channels] is read with ds_read_b64_tr_b16.
 // The K index of both PV operands uses the same permuted map (element e of lane group q <-> key 32 kj + 16 (e >> 2) + 4 q + (e & 3))
 // so that the transposing reads of a wave cover 512 contiguous bytes (conflict-free).
+#include <type_traits>
+
 #include "attn_mfma.h"
 
 typedef __attribute__((ext_vector_type(4))) short am_s16x4;
 typedef __attribute__((ext_vector_type(8))) short am_s16x8;
 typedef __attribute__((ext_vector_type(2))) uint32_t am_u32x2;
-
-#define AM_MAXL 64
 
 // window row of token l of window `win` (ws x ws windows, row-major over (frame, qh, qw))
 // Row of sequence element l of problem g = base(g) + off(l): the base is workgroup-uniform (scalar unit), the per-lane part is a shift and a
@@ -762,23 +762,6 @@ __global__ __launch_bounds__(256) void attn_mfma_bwd_shared_kernel(const float* 
   }
 }
 
-static int am_enabled() {   // read per call: tests switch the mode inside one process
-  const char* e = getenv("VPTR_ATTN_MFMA");
-  return e ? atoi(e) : 1;
-}
-
-// true when the MFMA kernels cover the geometry (otherwise the fp32 vector kernels of attn.hip run)
-bool vptr_attn_mfma_ok(int Lq, int Lk, int C, int nh, int causal, int64_t groups) {
-  const int hd = C / nh;
-  // VPTR_ATTN_MFMA: 0 = never, 1 (default) = problems with more than 16 rows (the 16-token fp32 vector kernels of attn.hip are
-  // faster on 16 x 16 problems: K64 step 56.9 vs 61.0 ms), 2 = every covered geometry
-  const int mode = am_enabled();
-  if (mode == 0 || (mode == 1 && Lq <= 16 && Lk <= 16)) return false;
-  // row offsets are 32-bit inside these kernels (am_derive): tensors of 2^31 or more elements take the fp32 vector kernels of attn.hip
-  if (groups * (int64_t)(Lq > Lk ? Lq : Lk) * C >= ((int64_t)1 << 31)) return false;
-  return Lq >= 1 && Lk >= 1 && Lq <= AM_MAXL && Lk <= AM_MAXL && hd % 2 == 0 && C % 2 == 0 && hd <= 96 && (!causal || Lq == Lk);
-}
-
 template <int NKS, int NDF>
 static int am_launch_fwd(const float* q, const float* k, const float* v, const float* table, const int64_t* rel_index, float* o, const AmGeom& gm, int causal,
                          float p, const uint64_t* seed_dev, uint32_t site, int p16, hipStream_t st) {
@@ -808,29 +791,36 @@ static int am_derive(const AmGeom& in, AmGeom& gm) {
   return 0;
 }
 
-int vptr_attn_mfma_fwd(const float* q, const float* k, const float* v, const float* table, const int64_t* rel_index, float* o, const AmGeom& gm_in, int causal,
-                       float p, const uint64_t* seed_dev, uint32_t site, int p16, hipStream_t st) {
+// launch(NKS, NDF) on the derived geometry with the route's template pair as integral constants
+template <class F>
+static int am_dispatch(const AmGeom& gm_in, const AttnRoute& r, F&& launch) {
   AmGeom gm;
   if (am_derive(gm_in, gm)) return -1;
-  const int nks = (gm.hd + 31) / 32, ndf = (gm.hd + 15) / 16;
-#define AM_CASE(NKS, NDF) if (nks == NKS && ndf == NDF) return am_launch_fwd<NKS, NDF>(q, k, v, table, rel_index, o, gm, causal, p, seed_dev, site, p16, st);
+#define AM_CASE(NKS, NDF) if (r.a == NKS && r.b == NDF) return launch(gm, std::integral_constant<int, NKS>{}, std::integral_constant<int, NDF>{});
   AM_CASE(1, 1) AM_CASE(1, 2) AM_CASE(2, 3) AM_CASE(2, 4) AM_CASE(3, 5) AM_CASE(3, 6)
 #undef AM_CASE
   vptr_set_error("attn_mfma: unsupported head dim %d", gm.hd);
   return -1;
 }
 
+int vptr_attn_mfma_fwd(const float* q, const float* k, const float* v, const float* table, const int64_t* rel_index, float* o, const AmGeom& gm_in,
+                       const AttnRoute& r, int causal, float p, const uint64_t* seed_dev, uint32_t site, int p16, hipStream_t st) {
+  return am_dispatch(gm_in, r, [&](const AmGeom& gm, auto NKS, auto NDF) {
+    return am_launch_fwd<decltype(NKS)::value, decltype(NDF)::value>(q, k, v, table, rel_index, o, gm, causal, p, seed_dev, site, p16, st);
+  });
+}
+
 template <int NKS, int NDF>
 static int am_launch_bwd(const float* q, const float* k, const float* v, const float* table, const int64_t* rel_index, const float* dout, float* dq, float* dk,
-                         float* dv, float* dtable, const AmGeom& gm, int causal, float p, const uint64_t* seed_dev, uint32_t site, float dq_scale, int p16,
-                         hipStream_t st) {
+                         float* dv, float* dtable, const AmGeom& gm, bool shared, int causal, float p, const uint64_t* seed_dev, uint32_t site, float dq_scale,
+                         int p16, hipStream_t st) {
   const int NQB = (gm.Lq + 15) / 16, nqbr = NQB == 1 ? 1 : (NQB == 2 ? 2 : 4), slots = 4 / nqbr;
   const int LKP = (gm.Lk + 31) / 32 * 32, pitch = LKP * 2 + 16;
   const int ntab = dtable ? (2 * gm.ws - 1) * (2 * gm.ws - 1) : 0;
   const size_t slot_bytes = (size_t)2 * NDF * LKP * 32 + (nqbr > 1 ? (size_t)LKP * NDF * 64 : 0) + (dtable ? ((ntab * 4 + 15) & ~15) : 0);
   const size_t lds = slots * slot_bytes + 4 * 2 * 16 * pitch;
   const int nprob = gm.groups * gm.nh;
-  if (nqbr > 1) {   // several query blocks per problem: the tile-sharing kernel
+  if (shared) {   // several query blocks per problem (nqbr > 1): the tile-sharing kernel
     const int LQ32 = (gm.Lq + 31) / 32 * 32, IMR = LKP > LQ32 ? LKP : LQ32;
     const size_t sb = (size_t)2 * NDF * IMR * 32 + (size_t)2 * NDF * LKP * 32 + (dtable ? ((ntab * 4 + 15) & ~15) : 0);   // K / dO / Q image, V image, table gradient
     const size_t lds2 = slots * sb + 4 * 4 * 16 * pitch;
@@ -847,14 +837,10 @@ static int am_launch_bwd(const float* q, const float* k, const float* v, const f
 }
 
 int vptr_attn_mfma_bwd(const float* q, const float* k, const float* v, const float* table, const int64_t* rel_index, const float* dout, float* dq, float* dk,
-                       float* dv, float* dtable, const AmGeom& gm_in, int causal, float p, const uint64_t* seed_dev, uint32_t site, float dq_scale, int p16,
-                       hipStream_t st) {
-  AmGeom gm;
-  if (am_derive(gm_in, gm)) return -1;
-  const int nks = (gm.hd + 31) / 32, ndf = (gm.hd + 15) / 16;
-#define AM_CASE(NKS, NDF) if (nks == NKS && ndf == NDF) return am_launch_bwd<NKS, NDF>(q, k, v, table, rel_index, dout, dq, dk, dv, dtable, gm, causal, p, seed_dev, site, dq_scale, p16, st);
-  AM_CASE(1, 1) AM_CASE(1, 2) AM_CASE(2, 3) AM_CASE(2, 4) AM_CASE(3, 5) AM_CASE(3, 6)
-#undef AM_CASE
-  vptr_set_error("attn_mfma: unsupported head dim %d", gm.hd);
-  return -1;
+                       float* dv, float* dtable, const AmGeom& gm_in, const AttnRoute& r, int causal, float p, const uint64_t* seed_dev, uint32_t site,
+                       float dq_scale, int p16, hipStream_t st) {
+  return am_dispatch(gm_in, r, [&](const AmGeom& gm, auto NKS, auto NDF) {
+    return am_launch_bwd<decltype(NKS)::value, decltype(NDF)::value>(q, k, v, table, rel_index, dout, dq, dk, dv, dtable, gm,
+                                                                     r.family == VPTR_ATTN_FAMILY_AM_SHARED, causal, p, seed_dev, site, dq_scale, p16, st);
+  });
 }

@@ -19,34 +19,59 @@ def _winattn_workspace(device, nh):
     return torch.empty((lib.vptr_winattn_bwd_workspace(int(nh)),), device=device, dtype=torch.float32)
 
 
+def _winattn_fwd(q, k, v, table, rel_index, geom, nh, p, seed, site, o_p16):
+    """vptr_winattn_fwd on contiguous q, k, v [B*H*W, C]; geom = (B, H, W, ws); returns o (a P16 tensor with o_p16)"""
+    B, H, W, ws = geom
+    o = torch.empty_like(q)
+    check(lib.vptr_winattn_fwd(ptr(q), ptr(k), ptr(v), ptr(table), ptr(rel_index), ptr(o), B, H, W, q.shape[1], nh, ws, p, ptr(seed), site,
+                               int(o_p16), stream()), "vptr_winattn_fwd")
+    return o
+
+
+def _winattn_bwd(q, k, v, table, rel_index, do, geom, nh, p, seed, site, dq_scale, p16):
+    """vptr_winattn_bwd_ws; returns dq (times dq_scale), dk, dv (P16 tensors with p16) and dtable -- None without a table, and None when the
+    table lives in a registered gradient slab: the kernel then added into the slab itself"""
+    B, H, W, ws = geom
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    slab = flat_grad_for(table)
+    dtable = slab if slab is not None else (torch.zeros_like(table) if table is not None else None)
+    wsp = _winattn_workspace(q.device, nh) if dtable is not None else None
+    check(lib.vptr_winattn_bwd_ws(ptr(q), ptr(k), ptr(v), ptr(table), ptr(rel_index), ptr(do), ptr(dq), ptr(dk), ptr(dv), ptr(dtable), B, H, W,
+                                  q.shape[1], nh, ws, p, ptr(seed), site, dq_scale, int(p16), ptr(wsp), wsp.numel() if wsp is not None else 0,
+                                  stream()), "vptr_winattn_bwd_ws")
+    return dq, dk, dv, (None if slab is not None else dtable)
+
+
+def _tattn_fwd(q, k, v, geom, nh, p, seed, site, o_p16):
+    """vptr_tattn_fwd on contiguous q [(n,tq,p), C], k, v [(n,tk,p), C]; geom = (Nb, Tq, Tk, HW, causal)"""
+    Nb, Tq, Tk, HW, causal = geom
+    o = torch.empty_like(q)
+    check(lib.vptr_tattn_fwd(ptr(q), ptr(k), ptr(v), ptr(o), Nb, Tq, Tk, HW, q.shape[1], nh, causal, p, ptr(seed), site, int(o_p16), stream()),
+          "vptr_tattn_fwd")
+    return o
+
+
+def _tattn_bwd(q, k, v, do, geom, nh, p, seed, site, dq_scale, p16):
+    Nb, Tq, Tk, HW, causal = geom
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    check(lib.vptr_tattn_bwd(ptr(q), ptr(k), ptr(v), ptr(do), ptr(dq), ptr(dk), ptr(dv), Nb, Tq, Tk, HW, q.shape[1], nh, causal, p, ptr(seed), site,
+                             dq_scale, int(p16), stream()), "vptr_tattn_bwd")
+    return dq, dk, dv
+
+
 class _WinAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, table, rel_index, B, H, W, nh, ws, p, site):
         q, k, v = _c(q), _c(k), _c(v)
-        C = q.shape[1]
-        o = torch.empty_like(q)
         ctx.seed = seed_tensor(q.device) if p > 0 else None
-        check(lib.vptr_winattn_fwd(ptr(q), ptr(k), ptr(v), ptr(table), ptr(rel_index), ptr(o), B, H, W, C, nh, ws, p,
-                                   ptr(ctx.seed), site, 0, stream()), "vptr_winattn_fwd")
+        ctx.cfg = ((B, H, W, ws), nh, p, site)
         ctx.save_for_backward(q, k, v, table, rel_index)
-        ctx.cfg = (B, H, W, nh, ws, p, site)
-        return o
+        return _winattn_fwd(q, k, v, table, rel_index, (B, H, W, ws), nh, p, ctx.seed, site, False)
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, table, rel_index = ctx.saved_tensors
-        B, H, W, nh, ws, p, site = ctx.cfg
-        do = _c(do)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        slab = flat_grad_for(table)
-        dtable = slab if slab is not None else (torch.zeros_like(table) if table is not None else None)
-        wsp = _winattn_workspace(q.device, nh) if dtable is not None else None
-        check(lib.vptr_winattn_bwd_ws(ptr(q), ptr(k), ptr(v), ptr(table), ptr(rel_index), ptr(do), ptr(dq), ptr(dk), ptr(dv),
-                                      ptr(dtable), B, H, W, q.shape[1], nh, ws, p, ptr(ctx.seed), site, 1.0, 0, ptr(wsp),
-                                      wsp.numel() if wsp is not None else 0, stream()), "vptr_winattn_bwd_ws")
-        if slab is not None:
-            dtable = None
-        return dq, dk, dv, dtable, None, None, None, None, None, None, None, None
+        geom, nh, p, site = ctx.cfg
+        return _winattn_bwd(*ctx.saved_tensors, _c(do), geom, nh, p, ctx.seed, site, 1.0, False) + (None,) * 8
 
 
 _WinAttnFn_apply = _direct_apply(_WinAttnFn)
@@ -61,24 +86,15 @@ class _TAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, Nb, Tq, Tk, HW, nh, causal, p, site):
         q, k, v = _c(q), _c(k), _c(v)
-        C = q.shape[1]
-        o = torch.empty_like(q)
         ctx.seed = seed_tensor(q.device) if p > 0 else None
-        check(lib.vptr_tattn_fwd(ptr(q), ptr(k), ptr(v), ptr(o), Nb, Tq, Tk, HW, C, nh, causal, p, ptr(ctx.seed), site,
-                                 0, stream()), "vptr_tattn_fwd")
+        ctx.cfg = ((Nb, Tq, Tk, HW, causal), nh, p, site)
         ctx.save_for_backward(q, k, v)
-        ctx.cfg = (Nb, Tq, Tk, HW, nh, causal, p, site)
-        return o
+        return _tattn_fwd(q, k, v, ctx.cfg[0], nh, p, ctx.seed, site, False)
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v = ctx.saved_tensors
-        Nb, Tq, Tk, HW, nh, causal, p, site = ctx.cfg
-        do = _c(do)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        check(lib.vptr_tattn_bwd(ptr(q), ptr(k), ptr(v), ptr(do), ptr(dq), ptr(dk), ptr(dv), Nb, Tq, Tk, HW, q.shape[1], nh,
-                                 causal, p, ptr(ctx.seed), site, 1.0, 0, stream()), "vptr_tattn_bwd")
-        return dq, dk, dv, None, None, None, None, None, None, None, None
+        geom, nh, p, site = ctx.cfg
+        return _tattn_bwd(*ctx.saved_tensors, _c(do), geom, nh, p, ctx.seed, site, 1.0, False) + (None,) * 8
 
 
 _TAttnFn_apply = _direct_apply(_TAttnFn)
@@ -209,16 +225,9 @@ class _ProjAttnFn(torch.autograd.Function):
             gemm_raw(xk, Wk, k, Mk, N, K, 0, 0, bias=bk, batch_extra=[(xv, Wv, v, bv, 1.0)])
         if kv_out is not None:   # the projected keys / values as the attention reads them (the decoding cache's prefill)
             kv_out(k, v)
-        o = torch.empty_like(q)
         ctx.seed = seed_tensor(dev) if p > 0 else None
-        if kind == 0:
-            B, H, W, ws = geom
-            check(lib.vptr_winattn_fwd(ptr(q), ptr(k), ptr(v), ptr(table), ptr(rel_index), ptr(o), B, H, W, N, nh, ws, p,
-                                       ptr(ctx.seed), site, int(o_p16), stream()), "vptr_winattn_fwd")
-        else:
-            Nb, Tq, Tk, HW, causal = geom
-            check(lib.vptr_tattn_fwd(ptr(q), ptr(k), ptr(v), ptr(o), Nb, Tq, Tk, HW, N, nh, causal, p, ptr(ctx.seed), site,
-                                     int(o_p16), stream()), "vptr_tattn_fwd")
+        o = (_winattn_fwd(q, k, v, table, rel_index, geom, nh, p, ctx.seed, site, o_p16) if kind == 0 else
+             _tattn_fwd(q, k, v, geom, nh, p, ctx.seed, site, o_p16))
         ctx.save_for_backward(xq, xk, xv, Wq, Wk, Wv, q, k, v, table, rel_index)
         ctx.bias_refs = (bq, bk, bv)   # the parameters (or views of them) themselves: gradient-destination lookup
         ctx.cfg = (kind, geom, nh, p, site, alpha, same_qk, same_v, merge_v, use)
@@ -232,22 +241,10 @@ class _ProjAttnFn(torch.autograd.Function):
         Mq, K = xq.shape
         Mk = xk.shape[0]
         N = Wq.shape[0]
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        dtable = None
         if kind == 0:
-            B, H, W, ws = geom
-            slab = flat_grad_for(table) if table is not None else None
-            dtable = slab if slab is not None else (torch.zeros_like(table) if table is not None else None)
-            wsp = _winattn_workspace(q.device, nh) if dtable is not None else None
-            check(lib.vptr_winattn_bwd_ws(ptr(q), ptr(k), ptr(v), ptr(table), ptr(rel_index), ptr(do), ptr(dq), ptr(dk), ptr(dv),
-                                          ptr(dtable), B, H, W, N, nh, ws, p, ptr(ctx.seed), site, alpha, int(use), ptr(wsp),
-                                          wsp.numel() if wsp is not None else 0, stream()), "vptr_winattn_bwd_ws")
-            if slab is not None:
-                dtable = None
+            dq, dk, dv, dtable = _winattn_bwd(q, k, v, table, rel_index, do, geom, nh, p, ctx.seed, site, alpha, use)
         else:
-            Nb, Tq, Tk, HW, causal = geom
-            check(lib.vptr_tattn_bwd(ptr(q), ptr(k), ptr(v), ptr(do), ptr(dq), ptr(dk), ptr(dv), Nb, Tq, Tk, HW, N, nh, causal, p,
-                                     ptr(ctx.seed), site, alpha, int(use), stream()), "vptr_tattn_bwd")
+            dq, dk, dv, dtable = _tattn_bwd(q, k, v, do, geom, nh, p, ctx.seed, site, alpha, use) + (None,)
         need = ctx.needs_input_grad
         rq, rk, rv = ctx.bias_refs
         dWq, dbq = _linear_param_grads(dq, xq, Wq, rq, need[3], need[4], p16=use)
