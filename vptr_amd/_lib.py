@@ -137,6 +137,10 @@ SIGNATURES = {
     "vptr_adamw": [P, P, P, P, L, F, F, F, F, F, P, P, F, F, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ["vptr_abi_version", "vptr_last_error"])
+# additive entry points declared in include/vptr_hip_ext.h (the ABI version and EXPORTS above stay as they are)
+EXT_SIGNATURES = {
+    "vptr_meters_add": [P, I, P, F, P],   # src: HOST array of K device pointers
+}
 
 
 def _load():
@@ -145,7 +149,7 @@ def _load():
             "vptr_amd: %s is missing. Build it with `python -m vptr_amd.build` (needs hipcc, gfx950). "
             "There is no CPU / PyTorch fallback for the VPTR hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argt in SIGNATURES.items():
+    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.argtypes = argt
         fn.restype = c_int

@@ -17,6 +17,8 @@ from pathlib import Path
 
 import torch
 
+from .meters import AverageMeters, BatchAverageMeter, gather_AverageMeters  # noqa: F401  (the other utils.train_summary names mirrored here)
+
 
 class LossTuple(object):
     """Per-loss history (utils/train_summary.py:92-95)."""

@@ -15,6 +15,10 @@ MI355X-first differences in *how* (not *what*):
 
 `FARTrainer` is the same for `single_iter` of train_FAR.py:48-101, `AETrainer` for the stage-1 auto-encoder + PatchGAN step of
 train_AutoEncoder.py:44-78; both NAR and FAR trainers take the optional adversarial branch (`disc=`, `lam_gan=`).
+
+Every trainer also has the `train_flag=False` branch of its `single_iter` as `eval_step` (eval mode, no_grad, nothing a step owns is
+written; `capture_eval` makes it a hipGraph of its own), `step` / `eval_step` feed a `meters.DeviceLossMeters` without a host read, and
+`run_epoch` is the reference's loop over a loader (train_NAR.py:231-247).
 """
 import os
 import time
@@ -51,6 +55,12 @@ def graph_node_census(g):
         name = _HIP_NODE_TYPES.get(t.value, "type%d" % t.value)
         out[name] = out.get(name, 0) + 1
     return out
+
+
+def _copy_into(dst, src):
+    """fill a captured graph's static input; a no-op when the caller wrote into that very tensor (`static_inputs`)"""
+    if src is not dst:
+        dst.copy_(src)
 
 
 DP_CHUNKS = 4  # grouped weight-gradient launches per step when gradients are exchanged between ranks
@@ -431,15 +441,23 @@ class NARTrainer:
         return self._finish(loss, dict({"T_total": loss.detach(), "T_GDL": l_gdl.detach(), "T_MSE": l_mse.detach(), "T_bpc": l_pc.detach()},
                                        **extra), front)
 
-    def step(self, past, future):
+    def step(self, past, future, meters=None):
+        """one train step (a replay when `capture` / `capture_front` ran); meters: a `meters.DeviceLossMeters` that receives the returned
+        terms in one launch issued behind the step -- outside any captured graph, so the meter can be swapped per epoch"""
+        out = self._step(past, future)
+        if meters is not None:
+            meters.update(out)
+        return out
+
+    def _step(self, past, future):
         if self._front is not None:
             # data-parallel step: forward + backward replayed as one hipGraph, then the part that talks to other ranks runs eagerly --
             # DP_CHUNKS grouped weight-gradient launches on the recorded operands (static addresses in the graph's pool), the all-reduces
             # between them, the optimizer (3 launches)
             if self.opt.planes is not None and self.opt.planes.stale():
                 self.opt.planes.refresh()
-            self._static_past.copy_(past)
-            self._static_future.copy_(future)
+            _copy_into(self._static_past, past)
+            _copy_into(self._static_future, future)
             if self._bufsync:
                 self._bufsync.sync()
             self._front.replay()
@@ -458,11 +476,19 @@ class NARTrainer:
             # round-1 corruption was a captured table upload reading a recycled pinned buffer: ops._to_device_async)
             if self.opt.planes is not None and self.opt.planes.stale():
                 self.opt.planes.refresh()   # parameters were changed from outside (load_state_dict) since the last replay
-            self._static_past.copy_(past)
-            self._static_future.copy_(future)
+            _copy_into(self._static_past, past)
+            _copy_into(self._static_future, future)
             self._graph.replay()
             return self._static_out
         return self._step_impl(past, future)
+
+    def _module_scratch(self):
+        """The frozen auto-encoder keeps shape-keyed scratch on its modules (plane, head and Winograd buffers) and replaces it when a
+        forward of another shape runs; a captured graph reads and writes the buffers of its capture by address, so it holds on to them --
+        otherwise an eager pass at another batch size (the fall-back of `eval_step`, `predict`) would hand their memory to the next
+        allocation and the following replay would write into it."""
+        return [getattr(m, a) for mod in (self.enc, self.dec) for m in mod.modules() for a in ("_plane_bufs", "_head_bufs", "_wino_bufs")
+                if getattr(m, a, None) is not None]
 
     @staticmethod
     def _warm_up_for_capture(warmup, step, any_rank=None):
@@ -513,7 +539,7 @@ class NARTrainer:
             raise RuntimeError("captured step holds node types that are not replay-safe on this HIP runtime: %s (all nodes: %s)"
                                % (bad, self.graph_nodes))
         g.instantiate()
-        self._graph = g
+        self._graph, self._graph_scratch = g, self._module_scratch()
         return g
 
     def capture_front(self, past, future, warmup=3):
@@ -549,7 +575,7 @@ class NARTrainer:
             raise RuntimeError("captured step holds node types that are not replay-safe on this HIP runtime: %s (all nodes: %s)"
                                % (bad, self.graph_nodes))
         g.instantiate()
-        self._front = g
+        self._front, self._graph_scratch = g, self._module_scratch()
         return g
 
     def _any_rank(self, flag):
@@ -576,6 +602,107 @@ class NARTrainer:
         self.opt.step(grad_scale=self._grad_scale)
         terms["grad_norm"] = self.opt.grad_norm()
         return terms
+
+    # -- validation pass: the train_flag=False branch of single_iter (train_NAR.py:88-100, train_FAR.py:85-94) ------------------------
+    _eval_graph = None
+
+    def _eval_disc(self, fake, real):
+        """cal_lossD, forward only (eval-mode discriminator): both clips flattened to frames, whatever their lengths"""
+        l_fake = self.gan(self.disc(fake.flatten(0, 1)), False)
+        l_real = self.gan(self.disc(real.flatten(0, 1)), True)
+        return {"Dtotal": (l_fake + l_real) * 0.5 * self.lam_gan, "Dfake": l_fake, "Dreal": l_real}
+
+    def _eval_forward(self, past, future):
+        if past.shape[0] == future.shape[0] and past.shape[2:] == future.shape[2:]:   # the concatenated call of _step_impl
+            feats = self.enc(torch.cat([past, future], dim=1))
+            past_feats, future_feats = feats[:, :past.shape[1]], feats[:, past.shape[1]:]
+        else:
+            past_feats, future_feats = self.enc(past), self.enc(future)
+        pred_feats = self.T(past_feats)
+        pred_frames = self.dec(pred_feats)
+        extra = self._eval_disc(pred_frames, future) if self.disc is not None else {}
+        loss, l_gdl, l_mse, l_pc = self.losses(pred_frames, future, pred_feats, future_feats)
+        if self.disc is not None:
+            extra["T_gan"] = self.gan(self.disc(pred_frames.flatten(0, 1)), True)
+            loss = loss + self.lam_gan * extra["T_gan"]
+        return dict({"T_total": loss, "T_GDL": l_gdl, "T_MSE": l_mse, "T_bpc": l_pc}, **extra)
+
+    @torch.no_grad()
+    def _eval_impl(self, past, future):
+        """Forward and losses with the transformer (and discriminator) in eval mode.  Nothing a train step owns is written: no optimizer
+        state, no gradient, no BatchNorm statistic (eval mode), no collective; the dropout master seed, which every transformer forward
+        advances, is put back, and so is the seed scope a pending backward would read."""
+        if self.T.training:
+            self.T.eval()
+        if self.disc is not None and self.disc.training:
+            self.disc.eval()
+        dev = past.device
+        key, seed = ops._dev_key(dev), ops._master_seed(dev)
+        scope, saved = ops._seed_scope.get(key), seed.clone()
+        try:
+            return self._eval_forward(past, future)
+        finally:
+            seed.copy_(saved)
+            if scope is None:
+                ops._seed_scope.pop(key, None)
+            else:
+                ops._seed_scope[key] = scope
+
+    def eval_step(self, past, future, meters=None):
+        """One validation iteration: the terms of `step` minus grad_norm, as 0-dim device tensors.  After `capture_eval` a batch of the
+        captured shapes is a replay of the eval graph; any other batch runs eagerly.  The next `step` puts the modules back into train
+        mode.  meters: as in `step`."""
+        g = self._eval_graph
+        if g is not None and past.shape == self._eval_past.shape and future.shape == self._eval_future.shape:
+            if self.opt.planes is not None and self.opt.planes.stale():
+                self.opt.planes.refresh()
+            _copy_into(self._eval_past, past)
+            _copy_into(self._eval_future, future)
+            g.replay()
+            out = self._eval_out
+        else:
+            out = self._eval_impl(past, future)
+        if meters is not None:
+            meters.update(out)
+        return out
+
+    def capture_eval(self, past, future, warmup=2):
+        """`capture` for the validation pass: eager warm-ups on a side stream, pinned staging reserved for the table uploads of one pass,
+        a single-stream capture, the node census (kernel / memcpy / empty nodes only).  The eval graph has static inputs and outputs of
+        its own, so it coexists with a train graph; it holds no collective, so it is allowed under a multi-rank group."""
+        self._eval_past, self._eval_future = past.clone(), future.clone()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(max(warmup, 1) - 1):
+                self._eval_impl(self._eval_past, self._eval_future)
+            ops._upload_stats.update(count=0, max_bytes=0)
+            self._eval_impl(self._eval_past, self._eval_future)
+        torch.cuda.current_stream().wait_stream(s)
+        ops.reserve_graph_staging(count=ops._upload_stats["count"] + 4, nbytes=max(1 << 16, 2 * ops._upload_stats["max_bytes"]))
+        g = torch.cuda.CUDAGraph(keep_graph=True)
+        with torch.cuda.graph(g):
+            out = self._eval_impl(self._eval_past, self._eval_future)
+        self.eval_graph_nodes = graph_node_census(g)
+        bad = {k: v for k, v in self.eval_graph_nodes.items() if k not in ("kernel", "memcpy", "empty")}
+        if bad:
+            g.reset()
+            raise RuntimeError("captured validation pass holds node types that are not replay-safe on this HIP runtime: %s (all nodes: %s)"
+                               % (bad, self.eval_graph_nodes))
+        g.instantiate()
+        self._eval_out, self._eval_graph, self._eval_scratch = out, g, self._module_scratch()
+        return g
+
+    def static_inputs(self, train=True):
+        """the (past, future) buffers the train (`capture` / `capture_front`) or eval (`capture_eval`) graph reads.  `step` / `eval_step`
+        skip their copy when handed exactly these tensors: write a batch there once -- `ClipIngest(...)(raw, out=trainer.static_inputs())`"""
+        if train:
+            if self._graph is None and self._front is None:
+                raise RuntimeError("static_inputs: capture() / capture_front() first")
+            return self._static_past, self._static_future
+        if self._eval_graph is None:
+            raise RuntimeError("static_inputs(train=False): capture_eval() first")
+        return self._eval_past, self._eval_future
 
     # -- replay == eager, checked on the live model (bench.py runs this before it times a graph) -------------------------------------
     def _snapshot(self):
@@ -719,6 +846,17 @@ class FARTrainer(NARTrainer):
             extra["T_gan"] = t_gan.detach()
         return self._finish(loss, dict({"T_total": loss.detach(), "T_GDL": l_gdl.detach(), "T_MSE": l_mse.detach()}, **extra), front)
 
+    def _eval_forward(self, past, future):
+        gt_feats = self.enc(torch.cat([past, future[:, :-1]], dim=1))        # train_FAR.py:53-55
+        pred_frames = self.dec(self.T(gt_feats))
+        extra = self._eval_disc(pred_frames, future) if self.disc is not None else {}   # cal_lossD(pred_frames, future_frames) :93
+        l_mse, l_gdl = ops.mse_gdl(pred_frames, torch.cat([past[:, 1:], future], dim=1))
+        loss = l_gdl + l_mse
+        if self.disc is not None:
+            extra["T_gan"] = self.gan(self.disc(pred_frames.flatten(0, 1)), True)
+            loss = loss + self.lam_gan * extra["T_gan"]
+        return dict({"T_total": loss, "T_GDL": l_gdl, "T_MSE": l_mse}, **extra)
+
     @torch.no_grad()
     def predict(self, past, num_pred, kv_cache=False):
         """Autoregressive test-phase rollout (train_FAR.py:103-125): see vptr_amd.inference.far_rollout (kv_cache: its KV-cached path)."""
@@ -744,7 +882,34 @@ class AETrainer:
         self.gan = GANLoss(gan_mode, target_real_label=1.0, target_fake_label=0.0).to(self.opt_G.flat.device)
         self.lam_gan = lam_gan
 
-    def step(self, past, future):
+    def step(self, past, future, meters=None):
+        out = self._step(past, future)
+        if meters is not None:
+            meters.update(out)
+        return out
+
+    @torch.no_grad()
+    def eval_step(self, past, future, meters=None):
+        """the train_flag=False branch of single_iter (train_AutoEncoder.py:75-82): Enc, Dec and the discriminator in eval mode,
+        cal_lossD and cal_lossG forward only; returns the keys of `step`.  Enc and Dec live in this trainer's optimizer slab, so
+        their eval-mode forward keeps no packed weight or BatchNorm fold (ops.weights_cacheable): the pass reads the parameters and
+        running statistics the last `step` left."""
+        for m in (self.enc, self.dec, self.disc):
+            if m.training:
+                m.eval()
+        x = torch.cat([past, future], dim=1)
+        rec = self.dec(self.enc(x))
+        l_fake = self.gan(self.disc(rec.flatten(0, 1)), False)
+        l_real = self.gan(self.disc(x.flatten(0, 1)), True)
+        l_gan = self.gan(self.disc(rec.flatten(0, 1)), True)
+        l_mse, l_gdl = ops.mse_gdl(rec, x)
+        out = {"AEgan": l_gan, "AE_MSE": l_mse, "AE_GDL": l_gdl, "AE_total": self.lam_gan * l_gan + l_mse + l_gdl,
+               "Dtotal": (l_fake + l_real) * 0.5 * self.lam_gan, "Dfake": l_fake, "Dreal": l_real}
+        if meters is not None:
+            meters.update(out)
+        return out
+
+    def _step(self, past, future):
         x = torch.cat([past, future], dim=1)
         if not self.enc.training:
             self.enc.train()
@@ -773,6 +938,27 @@ class AETrainer:
         self.opt_G.step()
         return {"AEgan": l_gan.detach(), "AE_MSE": l_mse.detach(), "AE_GDL": l_gdl.detach(), "AE_total": loss_G.detach(),
                 "Dtotal": loss_D.detach(), "Dfake": l_fake.detach(), "Dreal": l_real.detach()}
+
+
+def run_epoch(trainer, loader, train, meters, ingest=None):
+    """One epoch of the reference's loop (train_NAR.py:231-247): `step` (train) or `eval_step` over `loader` with every returned term
+    folded into `meters` on the device; nothing is read back, the caller's `meters.compute()` / `epoch_update()` is the epoch's one
+    sync.  ingest: a `data.ClipIngest`; the loader then yields uint8 clip batches, written as fp32 straight into the graph's static
+    inputs when the trainer has captured one for this mode and the batch fits it."""
+    fn = trainer.step if train else trainer.eval_step
+    static = None
+    if ingest is not None and (getattr(trainer, "_eval_graph", None) if not train
+                               else getattr(trainer, "_graph", None) or getattr(trainer, "_front", None)) is not None:
+        static = trainer.static_inputs(train=train)
+    for sample in loader:
+        if ingest is None:
+            past, future = sample
+        elif static is not None and sample.shape[0] == static[0].shape[0]:
+            past, future = ingest(sample, out=static)
+        else:
+            past, future = ingest(sample)
+        fn(past, future, meters=meters)
+    return meters
 
 
 def script_style_nar_iter(enc, dec, transformer, optimizer, past, future, mse_loss, gdl_loss, bpnce, lam_pc=0.1, max_grad_norm=1.0):
