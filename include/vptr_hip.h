@@ -106,7 +106,7 @@ typedef struct vptr_gemm_desc {
   int atomic;    /* 1: D += result (D must be initialised by the caller) */
   const float* colscale; /* [N] */
   const float* bias;     /* [N] */
-  float alpha;
+  float alpha;           /* alpha == 0 (a zero-initialised descriptor) is read as 1 by every launcher; likewise alpha_x1 / alpha_x2 of batch members */
   int act;
   const float* rowscale; /* [rs_mod] */
   int rs_div, rs_mod;

@@ -768,3 +768,92 @@ def nce_f32_emulation(g, p, frames, L, tau, gout):
         out.append((acc - x * (iv * dot)[:, None]) * iv[:, None])
     assert out[0].dtype == F and S.dtype == F
     return loss, out[0], out[1]
+
+
+# ---- the nt P16 GEMM through the C ABI (tests/test_01b_gemm_p16_abi_gpu.py): the launcher's conditions restated
+def gemm_p16_class(fields, cus):
+    """the launch class of a vptr_gemm call with P16 operands, restated from vptr_gemm_p16_launch and from the run-time choice of the EPI 0
+    instantiations (csrc/gemm_p16.hip).  fields: vptr_gemm_desc members by name, pointers as integer addresses (0 / missing = NULL), everything
+    missing = 0; cus: the device's compute units.  Returns (EPI, NST, epilogue) with epilogue "batched" (gemm_epilogue_rows_halves_batched),
+    "rows_halves" or "serial", or ("refuse", k) with k the launcher's VPTR_CHECK that refuses the descriptor, counted from 1 in source order."""
+    f = lambda k: fields.get(k, 0) or 0
+
+    def bits(*ks):
+        v = 0
+        for k in ks:
+            v |= int(f(k))
+        return v
+    if not (f("a_mode") == 5 and f("b_mode") == 3):
+        return ("refuse", 1)
+    if f("K") % 16 or f("lda") % 16 or f("ldb") % 16:
+        return ("refuse", 2)
+    if not (f("split_k") <= 1 and f("precision") == 3 and not f("a_rowsum") and not f("D_planes")):
+        return ("refuse", 3)
+    batch, ksegs = max(f("batch"), 1), max(f("ksegs"), 1)
+    sa, sb, sd = f("batch_stride_a"), f("batch_stride_b"), f("batch_stride_d")
+    strided = sd != 0
+    if strided and not (ksegs == 1 and batch <= 4096 and not any(f(k) for k in ("Dpre", "residual", "atomic", "batch_accum", "frame_stats", "act_grad_src",
+                                                                                "rowscale", "colscale", "act", "act_after")) and f("dropout_p") == 0
+                        and ((sa | sb | sd) & 15) == 0 and sa >= 0 and sb >= 0 and sd > 0):
+        return ("refuse", 4)
+    if not ((strided or batch <= 3) and ksegs <= 3 and (batch == 1 or ksegs == 1)):
+        return ("refuse", 5)
+    extra = 0 if strided else (batch if batch > 1 else ksegs) - 1
+    opb = bits("A", "B")
+    if extra >= 1:
+        if not (f("A_x1") and f("B_x1")):
+            return ("refuse", 6)
+        opb |= bits("A_x1", "B_x1")
+    if extra >= 2:
+        if not (f("A_x2") and f("B_x2")):
+            return ("refuse", 7)
+        opb |= bits("A_x2", "B_x2")
+    if opb & 63:
+        return ("refuse", 8)
+    members = batch > 1 and not strided
+    if members and not (f("D_x1") and (batch < 3 or f("D_x2")) and not f("Dpre") and not f("residual") and not f("atomic")):
+        return ("refuse", 9)
+    if f("rowscale") and not (f("rs_div") >= 1 and f("rs_mod") >= 1):
+        return ("refuse", 10)
+    p = f("dropout_p")
+    if p > 0 and not (f("seed_dev") and p < 1):
+        return ("refuse", 11)
+    N, ldd, ldr = f("N"), f("ldd"), f("ldr")
+    if f("d_p16") and not (not f("atomic") and N % 16 == 0 and ldd % 16 == 0 and ldr % 4 == 0 and (bits("D", "D_x1", "D_x2") & 63) == 0
+                           and (bits("residual", "bias", "colscale", "Dpre", "bias_x1", "bias_x2") & 15) == 0):
+        return ("refuse", 12)
+    tiles = -(-f("M") // 128) * -(-N // 176) * batch
+    ebits = bits("D", "residual", "bias")
+    if members:
+        ebits |= bits("D_x1", "D_x2", "bias_x1", "bias_x2")
+    vec = N % 4 == 0 and ldd % 4 == 0
+    plain = not f("colscale") and not f("Dpre") and not f("act_after") and not f("atomic")
+    lean = bool(plain and not f("rowscale") and f("act") == 0 and p == 0 and (ebits & 15) == 0 and vec and ldr % 4 == 0)
+    lean3 = bool(not lean and plain and (f("rowscale") or p > 0) and f("act") == 0 and not f("frame_stats") and (ebits & 15) == 0 and vec and ldr % 4 == 0)
+    lean4 = bool(not lean and not lean3 and not f("colscale") and not f("rowscale") and not f("residual") and not f("act_after") and not f("atomic")
+                 and f("act") != 0 and not f("act_grad_src") and not f("frame_stats") and batch == 1 and not f("batch_accum")
+                 and ((ebits | bits("Dpre")) & 15) == 0 and vec)
+    nst = 4 if tiles <= cus else 2
+    if f("frame_stats") and not (f("frame_rows") >= 64 and f("frame_rows") % 64 == 0 and f("M") % 64 == 0 and not f("act_grad_src") and lean and batch == 1):
+        return ("refuse", 13)
+    if f("act_grad_src"):
+        if not (not any(f(k) for k in ("colscale", "Dpre", "rowscale", "residual", "bias", "act_after", "atomic")) and batch == 1 and ksegs == 1
+                and f("act") != 0 and ((ebits | bits("act_grad_src")) & 15) == 0 and vec):
+            return ("refuse", 14)
+        return (2, nst, "batched")
+    if f("batch_accum") and not (lean and batch > 1 and not f("d_p16") and (f("batch_accum") >> batch) == 0):
+        return ("refuse", 15)
+    if lean4:
+        return (4, nst, "batched")
+    if lean3:
+        return (3, nst, "batched")
+    if lean:
+        return (1, nst, "batched")
+    # EPI 0 chooses in the kernel: epi_vec_ok looks at D, Dpre, residual, bias, colscale (+ the members' D / bias), N, ldd, ldr
+    vbits = bits("D", "Dpre", "residual", "bias", "colscale")
+    if members:
+        vbits |= bits("D_x1", "D_x2", "bias_x1", "bias_x2")
+    vec_ok = (vbits & 15) == 0 and vec and ldr % 4 == 0
+    if f("atomic") or not vec_ok:
+        return (0, nst, "serial")
+    return (0, nst, "batched" if nst == 4 else "rows_halves")

@@ -1538,3 +1538,110 @@ def test_step_tail_cases_against_emulation(part, capsys):
             C.run_dropout(be, n)
         for maxcount in C.DROPPATH_COUNTS:
             C.run_droppath(be, maxcount)
+
+
+# ---- the nt P16 GEMM through the C ABI (tests/test_01b_gemm_p16_abi_gpu.py): the launch-class mirror, the cases against a CPU emulation of the call,
+# the kink cap and the mutations of the emulation
+_G = dict(a_mode=5, b_mode=3, precision=3, M=300, N=528, K=144, lda=144, ldb=144, ldd=528, A=0x10000, B=0x20000, D=0x30000)     # 3 x 3 tiles
+_GX = dict(A_x1=0x11000, B_x1=0x21000, D_x1=0x31000, A_x2=0x12000, B_x2=0x22000, D_x2=0x32000)
+# written by hand from vptr_gemm_p16_launch and the EPI 0 branch of vptr_gemm_p16_kernel: (changes to _G, compute units, class)
+GEMM_P16_TABLE = [
+    (dict(), 256, (1, 4, "batched")), (dict(), 9, (1, 4, "batched")), (dict(), 8, (1, 2, "batched")), (dict(), 0, (1, 2, "batched")),
+    (dict(bias=0x40000, residual=0x50000, ldr=528, alpha=0.5), 256, (1, 4, "batched")),
+    (dict(bias=0x40004), 256, (0, 4, "serial")), (dict(bias=0x40004), 8, (0, 2, "serial")),
+    (dict(residual=0x50008, ldr=528), 256, (0, 4, "serial")), (dict(residual=0x50000, ldr=530), 8, (0, 2, "serial")),
+    (dict(N=50, ldd=52), 256, (0, 4, "serial")), (dict(ldd=530), 256, (0, 4, "serial")), (dict(D=0x30010), 256, (1, 4, "batched")),
+    (dict(rowscale=0x60004, rs_div=64, rs_mod=5), 256, (3, 4, "batched")), (dict(dropout_p=0.1, seed_dev=0x70000), 8, (3, 2, "batched")),
+    (dict(rowscale=0x60000, rs_div=1, rs_mod=1, dropout_p=0.1, seed_dev=0x70000, bias=0x40000, residual=0x50000, ldr=528, d_p16=1), 256, (3, 4, "batched")),
+    (dict(rowscale=0x60000, rs_div=0, rs_mod=1), 256, ("refuse", 10)), (dict(dropout_p=0.1), 256, ("refuse", 11)),
+    (dict(dropout_p=1.0, seed_dev=0x70000), 256, ("refuse", 11)),
+    (dict(act=1), 256, (4, 4, "batched")), (dict(act=3, Dpre=0x80000, dropout_p=0.1, seed_dev=0x70000, bias=0x40000, d_p16=1), 8, (4, 2, "batched")),
+    (dict(act=1, Dpre=0x80004), 256, (0, 4, "serial")), (dict(act=2, residual=0x50000, ldr=528), 256, (0, 4, "batched")),
+    (dict(act=2, residual=0x50000, ldr=528), 8, (0, 2, "rows_halves")), (dict(act=1, rowscale=0x60000, rs_div=1, rs_mod=1), 8, (0, 2, "rows_halves")),
+    (dict(act=1, batch=2, **_GX), 256, (0, 4, "batched")), (dict(act=1, ksegs=3, **_GX), 256, (4, 4, "batched")),
+    (dict(colscale=0x90000), 256, (0, 4, "batched")), (dict(colscale=0x90004), 8, (0, 2, "serial")), (dict(act_after=1), 8, (0, 2, "rows_halves")),
+    (dict(atomic=1), 256, (0, 4, "serial")), (dict(atomic=1), 8, (0, 2, "serial")), (dict(atomic=1, d_p16=1), 256, ("refuse", 12)),
+    (dict(act=1, act_grad_src=0xA0000), 256, (2, 4, "batched")), (dict(act=3, act_grad_src=0xA0000, dropout_p=0.1, seed_dev=0x70000, d_p16=1), 8, (2, 2, "batched")),
+    (dict(act_grad_src=0xA0000), 256, ("refuse", 14)), (dict(act=1, act_grad_src=0xA0004), 256, ("refuse", 14)),
+    (dict(act=1, act_grad_src=0xA0000, bias=0x40000), 256, ("refuse", 14)), (dict(act=1, act_grad_src=0xA0000, ksegs=2, **_GX), 256, ("refuse", 14)),
+    (dict(batch=3, **_GX), 27, (1, 4, "batched")), (dict(batch=3, **_GX), 26, (1, 2, "batched")), (dict(batch=3, bias_x2=0x41004, **_GX), 27, (0, 4, "serial")),
+    (dict(batch=2, batch_accum=2, **_GX), 256, (1, 4, "batched")), (dict(batch=2, batch_accum=4, **_GX), 256, ("refuse", 15)),
+    (dict(batch=2, batch_accum=1, d_p16=1, **_GX), 256, ("refuse", 15)), (dict(batch_accum=1), 256, ("refuse", 15)),
+    (dict(batch=2, batch_accum=1, act=1, **_GX), 256, ("refuse", 15)),
+    (dict(batch=2, A_x1=0x11000, B_x1=0x21000), 256, ("refuse", 9)), (dict(batch=2, residual=0x50000, ldr=528, **_GX), 256, ("refuse", 9)),
+    (dict(batch=3, A_x1=0x11000, B_x1=0x21000, D_x1=0x31000), 256, ("refuse", 7)), (dict(batch=2), 256, ("refuse", 6)), (dict(ksegs=2, A_x1=0x11000), 256, ("refuse", 6)),
+    (dict(batch=4, **_GX), 256, ("refuse", 5)), (dict(ksegs=4, **_GX), 256, ("refuse", 5)), (dict(batch=2, ksegs=2, **_GX), 256, ("refuse", 5)),
+    (dict(batch=40, batch_stride_a=4800, batch_stride_b=0, batch_stride_d=16 * 528 * 20), 256, (1, 2, "batched")),
+    (dict(batch=28, batch_stride_a=4800, batch_stride_b=16, batch_stride_d=16 * 528 * 20, d_p16=1, bias=0x40000), 252, (1, 4, "batched")),
+    (dict(batch=2, batch_stride_a=4800, batch_stride_b=0, batch_stride_d=528 * 300 + 8), 256, ("refuse", 4)),
+    (dict(batch=2, batch_stride_a=4800, batch_stride_b=0, batch_stride_d=16 * 528 * 20, act=1), 256, ("refuse", 4)),
+    (dict(batch=2, batch_stride_a=-16, batch_stride_b=0, batch_stride_d=16 * 528 * 20), 256, ("refuse", 4)),
+    (dict(batch=5000, batch_stride_a=0, batch_stride_b=0, batch_stride_d=16 * 528 * 20), 256, ("refuse", 4)),
+    (dict(frame_stats=0xB0000, frame_rows=64, M=320), 256, (1, 4, "batched")), (dict(frame_stats=0xB0000, frame_rows=192, M=320, residual=0x50000, ldr=528), 8, (1, 2, "batched")),
+    (dict(frame_stats=0xB0000, frame_rows=64), 256, ("refuse", 13)), (dict(frame_stats=0xB0000, frame_rows=96, M=320), 256, ("refuse", 13)),
+    (dict(frame_stats=0xB0000, frame_rows=64, M=320, dropout_p=0.1, seed_dev=0x70000), 256, ("refuse", 13)),
+    (dict(frame_stats=0xB0000, frame_rows=64, M=320, batch=2, **_GX), 256, ("refuse", 13)),
+    (dict(d_p16=1), 256, (1, 4, "batched")), (dict(d_p16=1, N=100, ldd=112), 256, ("refuse", 12)), (dict(d_p16=1, ldd=536), 256, ("refuse", 12)),
+    (dict(d_p16=1, D=0x30010), 256, ("refuse", 12)), (dict(d_p16=1, bias=0x40004), 256, ("refuse", 12)),
+    (dict(K=24), 256, ("refuse", 2)), (dict(lda=152), 256, ("refuse", 2)), (dict(precision=1), 256, ("refuse", 3)), (dict(split_k=2), 256, ("refuse", 3)),
+    (dict(a_rowsum=0xC0000), 256, ("refuse", 3)), (dict(a_mode=0), 256, ("refuse", 1)), (dict(b_mode=0), 256, ("refuse", 1)),
+    (dict(A=0x10010), 256, ("refuse", 8)), (dict(ksegs=2, A_x1=0x11020, B_x1=0x21000), 256, ("refuse", 8)),
+]
+
+
+def test_gemm_p16_class_table():
+    """helpers.gemm_p16_class against a table written by hand from the launcher's conditions and the run-time choice of the EPI 0 kernels"""
+    from helpers import gemm_p16_class
+    bad = []
+    for change, cus, want in GEMM_P16_TABLE:
+        got = gemm_p16_class(dict(_G, **change), cus)
+        if got != want:
+            bad.append((change, cus, got, want))
+    assert not bad, bad
+    assert {w for _, _, w in GEMM_P16_TABLE if w[0] != "refuse"} == set(__import__("gemm_p16_cases").CLASSES)
+    assert {w[1] for _, _, w in GEMM_P16_TABLE if w[0] == "refuse"} == set(range(1, 16))
+
+
+@pytest.mark.parametrize("cus", [16, 256, 304])
+def test_gemm_p16_cases_cover_every_launch_class(cus):
+    """each of the twelve classes is run by at least two cases whatever the compute-unit count (the NST = 2 geometries grow with it); every case
+    asserts its class while it is built"""
+    import gemm_p16_cases as C
+    census = C.class_census(cus)
+    assert len(census) == 12 and all(len(v) >= 2 for v in census.values()), {k: len(v) for k, v in census.items()}
+    assert sum(len(v) for v in census.values()) == len(C.CASES)
+
+
+@pytest.mark.parametrize("part", range(4))
+def test_gemm_p16_cases_against_emulation(part, capsys):
+    """every case of tests/test_01b_gemm_p16_abi_gpu.py against the fp32 CPU emulation of the call (16 compute units): descriptors, pitches,
+    guards, references and bars of the CASES; the emulation's fp32 arithmetic stays inside every bar and leaves at most 1 % of a case's elements
+    to the kink rule (asserted per case by the runner)"""
+    import gemm_p16_cases as C
+    be = C.EmuBackend()
+    for cid in C.CASES[part::4]:
+        _, figures = C.run_case(be, cid)
+        assert all(w <= 1.0 and r < C.TOL3 for w, r in figures)
+    if part == 0:
+        for k in C.REJECTS:
+            C.run_reject(be, k)
+
+
+# mutation -> cases that have to notice it (a few each; at least one must fail)
+GEMM_P16_MUTATION_CASES = {
+    "tail_not_zeroed": ["e1_bias_alpha-g10", "e1_bias_alpha-g129", "e1_bias_alpha-n1"], "seg3_reads_seg2": ["e1_kseg3-g129", "e3_both_kseg3-n72"],
+    "col_plus4": ["e0_n50-g129n50", "e0_n50-n1n50"], "drop_index_ldd": ["e3_drop-g129", "e4_gelu-g129", "e2_drop-g129"],
+    "rs_div_ignored": ["e3_rs-g129", "e0_act_rs_res-g129"], "accum_ignored": ["e1_accum6-g129", "e1_accum7-g129"],
+    "dpre_after_act": ["e4_gelu-g129", "e4_lrelu-g129"], "grad_src_pitch_n": ["e2_gelu-g129", "e2_relu-g129"], "p16_without_lo": ["e1_p16-g129", "e1_strided_p16-sb4"],
+}
+
+
+@pytest.mark.parametrize("mut", sorted(GEMM_P16_MUTATION_CASES))
+def test_gemm_p16_cases_notice_mutations(mut, capsys):
+    """each named mutation of the emulation makes every case listed for it fail (and the unmutated emulation passes them, above)"""
+    import gemm_p16_cases as C
+    assert sorted(GEMM_P16_MUTATION_CASES) == sorted(C.MUTATIONS)
+    be = C.EmuBackend(mut=mut)
+    for cid in GEMM_P16_MUTATION_CASES[mut]:
+        with pytest.raises(AssertionError):
+            C.run_case(be, cid)

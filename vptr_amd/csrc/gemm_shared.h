@@ -408,7 +408,7 @@ __device__ __forceinline__ void gemm_epilogue_rows_halves_batched(const vptr_gem
         for (int e = 0; e < 4; ++e) {
           float t = GRAD ? v[e] * vptr_act_grad(res[it][e], act) : vptr_act(v[e], act) * rs;
           if (dropout_p > 0.f) t *= vptr_drop_scale(seed, p.site, (uint64_t)row * (uint64_t)p.N + col + e, dropout_p);
-          if (!GRAD) t += res[it][e];
+          t += GRAD ? 0.f : res[it][e];   // GRAD: a dropped element is +0 like everywhere else (x * 0 alone keeps the sign of x)
           if (act_after) t = t > 0.f ? t : 0.f;
           v[e] = t;
         }
