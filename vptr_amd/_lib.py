@@ -141,6 +141,11 @@ EXPORTS = sorted(list(SIGNATURES) + ["vptr_abi_version", "vptr_last_error"])
 EXT_SIGNATURES = {
     "vptr_meters_add": [P, I, P, F, P],   # src: HOST array of K device pointers
 }
+# device-resident optimizer controls declared in include/vptr_hip_optim.h (additive as well: neither in EXPORTS nor in EXT_SIGNATURES)
+OPTIM_SIGNATURES = {
+    "vptr_optim_prepare": [P, P, P, P, P],
+    "vptr_adamw_ctl": [P, P, P, P, L, P, P],
+}
 
 
 def _load():
@@ -149,7 +154,7 @@ def _load():
             "vptr_amd: %s is missing. Build it with `python -m vptr_amd.build` (needs hipcc, gfx950). "
             "There is no CPU / PyTorch fallback for the VPTR hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.argtypes = argt
         fn.restype = c_int

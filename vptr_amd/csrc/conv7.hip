@@ -770,6 +770,20 @@ __global__ __launch_bounds__(256) void conv7_dw_reduce_kernel(const float* __res
   __syncthreads();
   if (qd == 0) dw[((int64_t)co * 64 + ci) * 49 + tap] += (part[0][ci] + part[1][ci]) + (part[2][ci] + part[3][ci]);
 }
+// Deterministic mode: the bias gradient in a fixed order -- one workgroup per output channel walks that channel's B * H * W activation
+// gradients with a fixed thread assignment (conv7_out_bwd_weight2_kernel adds 8 wave sums per workgroup onto db with atomics)
+__global__ __launch_bounds__(256) void conv7_out_db_kernel(const float* __restrict__ dy, const float* __restrict__ y, float* __restrict__ db, int B,
+                                                           int HW, int Cimg, int out_act) {
+  __shared__ float red[16];
+  const int co = blockIdx.x;
+  float s = 0.f;
+  for (int64_t i = threadIdx.x; i < (int64_t)B * HW; i += 256) {
+    const int64_t o = ((i / HW) * Cimg + co) * HW + i % HW;
+    s += out_act_grad(dy[o], y[o], out_act);
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) db[co] += s;
+}
 extern "C" int vptr_conv7_out_bwd_weight_workspace(int B, int Cimg) { return B * C7_BANDS * Cimg * 49 * 64; }
 extern "C" int vptr_conv7_out_bwd_weight_ws(const float* dy, const float* y, const float* x, float* dw, float* db, int B, int Cin,
                                             int H, int W, int Cimg, int out_act, float* workspace, int workspace_floats,
@@ -783,8 +797,13 @@ extern "C" int vptr_conv7_out_bwd_weight_ws(const float* dy, const float* y, con
   VPTR_CHECK((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "conv7_out_bwd_weight: the workspace must be 16-byte aligned");
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute((const void*)conv7_out_bwd_weight2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  conv7_out_bwd_weight2_kernel<<<B * C7_BANDS, 512, lds, (hipStream_t)stream>>>(dy, y, x, workspace, db, B, H, W, Cimg, out_act);
+  const bool det_db = g_vptr_deterministic && db;
+  conv7_out_bwd_weight2_kernel<<<B * C7_BANDS, 512, lds, (hipStream_t)stream>>>(dy, y, x, workspace, det_db ? nullptr : db, B, H, W, Cimg, out_act);
   VPTR_LAUNCH_CHECK();
+  if (det_db) {
+    conv7_out_db_kernel<<<Cimg, 256, 0, (hipStream_t)stream>>>(dy, y, db, B, H * W, Cimg, out_act);
+    VPTR_LAUNCH_CHECK();
+  }
   conv7_dw_reduce_kernel<<<49 * Cimg, 256, 0, (hipStream_t)stream>>>(workspace, dw, B * C7_BANDS, Cimg);
   VPTR_LAUNCH_CHECK();
   return 0;
@@ -1015,13 +1034,14 @@ extern "C" int vptr_reflect_fold(const float* dxpad, float* dx, int B, int H, in
 
 // ---------------------------------------------------------------------------------------------------------------------
 // weight gradient of the 7x7 input convolution (Cout = 64): thread = (output channel, tap group of 4); a workgroup sweeps a
-// chunk of pixels, every thread accumulating its taps in registers, and leaves Cimg*49 atomics per channel.
+// chunk of pixels, every thread accumulating its taps in registers, and leaves Cimg*49 atomics per channel.  Deterministic mode: ONE
+// workgroup sweeps all pixels (chunk = npix), so every destination has one adder.
 #define C7W_CHUNK 2048
 __global__ __launch_bounds__(256) void conv7_in_bwd_weight_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                                  float* __restrict__ dw, int B, int Cimg, int H, int W) {
+                                                                  float* __restrict__ dw, int B, int Cimg, int H, int W, int64_t chunk) {
   const int co = threadIdx.x & 63, tg = threadIdx.x >> 6;  // taps tg, tg + 4, ... < 49 (13 or 12 per thread)
   const int64_t npix = (int64_t)B * H * W;
-  const int64_t p0 = (int64_t)blockIdx.x * C7W_CHUNK, p1 = p0 + C7W_CHUNK < npix ? p0 + C7W_CHUNK : npix;
+  const int64_t p0 = (int64_t)blockIdx.x * chunk, p1 = p0 + chunk < npix ? p0 + chunk : npix;
   for (int ci = 0; ci < Cimg; ++ci) {
     float acc[13];
 #pragma unroll
@@ -1050,7 +1070,8 @@ extern "C" int vptr_conv7_in_bwd_weight(const float* dy, const float* x, float* 
   VPTR_CHECK(dy && x && dw && B > 0 && Cimg > 0 && H > 3 && W > 3, "conv7_in_bwd_weight: bad arguments");
   VPTR_CHECK(Cout == 64, "conv7_in_bwd_weight: Cout must be 64 (ngf of the reference encoder), got %d", Cout);
   const int64_t npix = (int64_t)B * H * W;
-  conv7_in_bwd_weight_kernel<<<(unsigned)cdiv(npix, C7W_CHUNK), 256, 0, (hipStream_t)stream>>>(dy, x, dw, B, Cimg, H, W);
+  const int64_t chunk = g_vptr_deterministic ? npix : C7W_CHUNK;
+  conv7_in_bwd_weight_kernel<<<(unsigned)cdiv(npix, chunk), 256, 0, (hipStream_t)stream>>>(dy, x, dw, B, Cimg, H, W, chunk);
   VPTR_LAUNCH_CHECK();
   return 0;
 }

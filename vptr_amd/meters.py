@@ -103,10 +103,11 @@ class _HipAdd:
 class DeviceLossMeters:
     """Per-term running records ([K, 8] fp64: sum, sum of squares, count, non-finite count, last value) of up to 16 loss terms.
 
-    names: the loss names (a `loss_name_list`); `ignore`: keys a step returns that are deliberately not metered ('grad_norm').
+    names: the loss names (a `loss_name_list`); `ignore`: keys a step returns that are deliberately not metered ('grad_norm' and what a
+    step with optimizer controls adds, 'lr' / 'skipped' ...; any of them is metered when it is listed in `names`).
     add: backend `add(terms, state, weight)` with `terms` the K tensors in row order (None = absent); default: the HIP kernel."""
 
-    def __init__(self, names, device, ignore=("grad_norm",), add=None):
+    def __init__(self, names, device, ignore=("grad_norm", "lr", "skipped", "lr_G", "lr_D", "skipped_G", "skipped_D"), add=None):
         self.names = list(names)
         if not 1 <= len(self.names) <= MAX_TERMS or len(set(self.names)) != len(self.names):
             raise ValueError("DeviceLossMeters: 1 .. %d distinct names, got %r" % (MAX_TERMS, self.names))

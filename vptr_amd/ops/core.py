@@ -59,7 +59,9 @@ def set_deterministic(on=True):
     / BAIR-64 attention -- on one device): the launchers of the library stop letting workgroups meet in fp32 atomics
     (vptr_set_deterministic: one adder per destination for the BatchNorm-type norm-act column sums, the depthwise-convolution weight
     gradients, row-table and column sums), the conv-FFN frame statistics go back to their own fixed-order pass, and `FlatAdamW` takes
-    the gradient norm through a fixed-order two-pass sum.  The default path keeps the atomics (they are faster; the reference's
+    the gradient norm through a fixed-order two-pass sum.  The discriminator and the stage-1 auto-encoder step are covered too: the
+    convolution weight-gradient GEMMs run without K-splits (ops.wgrad._split_k_for), the 7x7 input convolution's weight gradient on one
+    workgroup, the 7x7 output convolution's bias gradient in a fixed-order pass of its own.  The default path keeps the atomics (they are faster; the reference's
     cuDNN / cuBLAS path is not bit-deterministic either).  Slower: the single-adder geometries serialise ~40 small reductions per step.
     Also: VPTR_DETERMINISTIC=1 in the environment.  tests/test_11_deterministic_gpu.py runs steps twice and compares bit for bit."""
     on = bool(on)

@@ -465,7 +465,8 @@ def flush_wgrads(chunks=1, on_chunk=None):
 
 
 def _split_k_for(tiles, K):
-    """Enough K-splits to put >= ~512 workgroups on the 256 CUs, each split >= 256 deep."""
-    if tiles >= 384:
+    """Enough K-splits to put >= ~512 workgroups on the 256 CUs, each split >= 256 deep.  Deterministic mode: one split, so that every
+    destination has one adder (the splits meet in fp32 atomics, whose order changes the last bits run to run)."""
+    if tiles >= 384 or config.deterministic:
         return 1
     return max(1, min((512 + tiles - 1) // tiles, K // 256))

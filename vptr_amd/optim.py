@@ -1,0 +1,183 @@
+"""Device-resident optimizer controls: learning-rate schedules and the non-finite skip of `train.FlatAdamW` (csrc/optim.hip,
+include/vptr_hip_optim.h).
+
+`vptr_adamw` takes its hyper-parameters by value, so a captured step (`NARTrainer.capture`) freezes them into the graph.  With controls the
+hyper-parameters live in a 64-byte device record (`hyper`); `vptr_optim_prepare` -- one single-lane launch behind the gradient's sum of
+squares -- decides whether the step is usable, advances the step counter, evaluates the schedule and leaves the launch-uniform scalars of
+the update in a second record (`state`), which `vptr_adamw_ctl` reads.  Everything the host changes is a stream-ordered write of a `hyper`
+word, so it takes effect on the next step whether that step is eager or a graph replay.
+
+`LRSchedule` is the host mirror of the schedule the kernel evaluates: `base_lr * schedule.factor(k)` is the rate of the update that follows
+k applied updates, which is what `torch.optim.lr_scheduler.LambdaLR(opt, schedule.factor)` gives with `scheduler.step()` after each
+`optimizer.step()`.
+"""
+import math
+
+import numpy as np
+import torch
+
+from ._lib import check, lib, ptr, stream
+
+# word indices of the two records (include/vptr_hip_optim.h)
+H_BASE_LR, H_BETA1, H_BETA2, H_EPS, H_WEIGHT_DECAY, H_MAX_NORM, H_GRAD_SCALE, H_SKIP_NONFINITE = range(8)
+H_SCHED_KIND, H_WARMUP_STEPS, H_TOTAL_STEPS, H_MIN_RATIO = range(8, 12)
+S_LR_NOW, S_GRAD_NORM, S_SKIP_NOW, S_SKIPPED_TOTAL, S_SKIPPED_IN_A_ROW, S_COEF, S_STEP_SIZE, S_INV_SQRT_BC2, S_DECAY, S_OB1, S_OB2 = range(11)
+S_BETA1, S_BETA2, S_EPS = 11, 12, 13
+WORDS = 16
+MAX_STEPS = 1 << 24        # W and S travel as fp32 words, and the step counter is an fp32 too: whole numbers are exact below 2^24
+
+KINDS = ("constant", "linear", "cosine")
+STATE_KEY = "vptr_controls"   # the key `FlatAdamW.state_dict` adds to param_groups[0]
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+class LRSchedule:
+    """Warm-up + decay as a factor on the base rate.  With k the number of updates already applied, W = warmup_steps, S = total_steps,
+    r = min_ratio:
+
+        k < W:   factor = (k + 1) / W                               (linear warm-up that ends at 1, never starts at 0)
+        else     t = min(1, (k - W) / max(1, S - W))
+                 constant: 1;   linear: 1 - (1 - r) t;   cosine: r + (1 - r) (1 + cos(pi t)) / 2
+
+    so the factor stays at r from k = S on.  `total_steps` may be omitted for the constant kind only.  `min_ratio` is held as the fp32
+    value the device record stores, so `factor` is the exact mirror of what the kernel evaluates (in fp64, like here)."""
+
+    def __init__(self, kind="constant", warmup_steps=0, total_steps=None, min_ratio=0.0):
+        if kind not in KINDS:
+            raise ValueError("LRSchedule: kind must be one of %r, got %r" % (KINDS, kind))
+        for name, val in (("warmup_steps", warmup_steps), ("total_steps", total_steps)):
+            if val is None and name == "total_steps":
+                continue
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or not 0 <= val < MAX_STEPS:
+                raise ValueError("LRSchedule: %s must be a whole number in [0, 2^24), got %r" % (name, val))
+        if total_steps is None:
+            if kind != "constant":
+                raise ValueError("LRSchedule: kind %r needs total_steps" % kind)
+            total_steps = warmup_steps
+        if total_steps < warmup_steps:
+            raise ValueError("LRSchedule: total_steps %d is below warmup_steps %d" % (total_steps, warmup_steps))
+        if isinstance(min_ratio, bool) or not isinstance(min_ratio, (int, float, np.floating)) or not (math.isfinite(min_ratio) and 0.0 <= min_ratio <= 1.0):
+            raise ValueError("LRSchedule: min_ratio must be a number in [0, 1], got %r" % (min_ratio,))
+        self.kind, self.warmup_steps, self.total_steps, self.min_ratio = kind, int(warmup_steps), int(total_steps), _f32(min_ratio)
+
+    def factor(self, k):
+        """the factor of the update that follows k applied updates (Python floats)"""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError("LRSchedule.factor: k must be a whole number >= 0, got %r" % (k,))
+        W, S, r = self.warmup_steps, self.total_steps, self.min_ratio
+        if k < W:
+            return (k + 1.0) / W
+        if self.kind == "constant":
+            return 1.0
+        t = min(1.0, (k - W) / max(1.0, float(S - W)))
+        if self.kind == "linear":
+            return 1.0 - (1.0 - r) * t
+        return r + (1.0 - r) * (1.0 + math.cos(math.pi * t)) / 2.0
+
+    def words(self):
+        """(sched_kind, W, S, r) as the `hyper` record holds them"""
+        return float(KINDS.index(self.kind)), float(self.warmup_steps), float(self.total_steps), self.min_ratio
+
+    def to_dict(self):
+        return {"kind": self.kind, "warmup_steps": self.warmup_steps, "total_steps": self.total_steps, "min_ratio": self.min_ratio}
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(d["kind"], d["warmup_steps"], d["total_steps"], d["min_ratio"])
+
+    def __eq__(self, other):
+        return isinstance(other, LRSchedule) and self.to_dict() == other.to_dict()
+
+    def __repr__(self):
+        return "LRSchedule(kind=%r, warmup_steps=%d, total_steps=%d, min_ratio=%r)" % (self.kind, self.warmup_steps, self.total_steps, self.min_ratio)
+
+
+def _finite(name, x, lo=None, lo_open=False, hi=None, hi_open=False):
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.floating, np.integer)) or not math.isfinite(x):
+        raise ValueError("optimizer controls: %s must be a finite number, got %r" % (name, x))
+    if lo is not None and (x <= lo if lo_open else x < lo) or hi is not None and (x >= hi if hi_open else x > hi):
+        raise ValueError("optimizer controls: %s = %r is out of range" % (name, x))
+    return float(x)
+
+
+class OptimControls:
+    """The two device records of one optimizer and the launches on them.  `hyper` is written by the host only, one fill kernel per changed
+    word (stream-ordered, no memset node, no host buffer whose lifetime a graph would have to care about); `state` is written by the device
+    only, apart from the zeroing here and `load_counters`."""
+
+    def __init__(self, device, lr, betas, eps, weight_decay, max_grad_norm, schedule=None, skip_nonfinite=False):
+        if schedule is not None and not isinstance(schedule, LRSchedule):
+            raise TypeError("optimizer controls: schedule must be an LRSchedule, got %r" % (schedule,))
+        buf = torch.zeros(2 * WORDS, device=device, dtype=torch.float32)
+        self.hyper, self.state = buf[:WORDS], buf[WORDS:]
+        if self.hyper.data_ptr() % 64 or self.state.data_ptr() % 64:
+            raise RuntimeError("optimizer controls: the allocator returned a record that is not 64-byte aligned")
+        self.schedule = schedule if schedule is not None else LRSchedule()
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._host = [None] * WORDS      # what the host last wrote into each word
+        self.write(lr, betas, eps, weight_decay, max_grad_norm, 1.0)
+
+    # -- hyper ------------------------------------------------------------------------------------------------------------------
+    def _put(self, idx, value):
+        value = _f32(value)
+        if self._host[idx] != value:
+            self.hyper[idx:idx + 1].fill_(value)
+            self._host[idx] = value
+
+    def write(self, lr, betas, eps, weight_decay, max_grad_norm, grad_scale):
+        """validate and write every word"""
+        self.set_lr(lr)
+        self._put(H_BETA1, _finite("beta1", betas[0], 0.0, False, 1.0, True))
+        self._put(H_BETA2, _finite("beta2", betas[1], 0.0, False, 1.0, True))
+        self._put(H_EPS, _finite("eps", eps, 0.0))
+        self.set_weight_decay(weight_decay)
+        self.set_max_grad_norm(max_grad_norm)
+        self.set_grad_scale(grad_scale)
+        self._put(H_SKIP_NONFINITE, 1.0 if self.skip_nonfinite else 0.0)
+        self.set_schedule(self.schedule)
+
+    def set_lr(self, lr):
+        self._put(H_BASE_LR, _finite("lr", lr, 0.0))
+
+    def set_weight_decay(self, weight_decay):
+        self._put(H_WEIGHT_DECAY, _finite("weight_decay", weight_decay, 0.0))
+
+    def set_max_grad_norm(self, max_grad_norm):
+        """None (or a value <= 0): no clipping"""
+        self._put(H_MAX_NORM, 0.0 if max_grad_norm is None else max(0.0, _finite("max_grad_norm", max_grad_norm)))
+
+    def set_grad_scale(self, grad_scale):
+        self._put(H_GRAD_SCALE, _finite("grad_scale", grad_scale, 0.0, True))
+
+    def set_schedule(self, schedule):
+        if schedule is None:
+            schedule = LRSchedule()
+        if not isinstance(schedule, LRSchedule):
+            raise TypeError("optimizer controls: schedule must be an LRSchedule, got %r" % (schedule,))
+        self.schedule = schedule
+        for idx, w in zip((H_SCHED_KIND, H_WARMUP_STEPS, H_TOTAL_STEPS, H_MIN_RATIO), schedule.words()):
+            self._put(idx, w)
+
+    # -- state ------------------------------------------------------------------------------------------------------------------
+    def word(self, idx):
+        """0-dim fp32 view of a `state` word"""
+        return self.state[idx]
+
+    def counters(self):
+        """(skipped_total, skipped_in_a_row) read back (one sync)"""
+        t, r = self.state[S_SKIPPED_TOTAL:S_SKIPPED_IN_A_ROW + 1].tolist()
+        return t, r
+
+    def load_counters(self, total, in_a_row):
+        self.state[S_SKIPPED_TOTAL:S_SKIPPED_TOTAL + 1].fill_(float(total))
+        self.state[S_SKIPPED_IN_A_ROW:S_SKIPPED_IN_A_ROW + 1].fill_(float(in_a_row))
+
+    # -- launches ---------------------------------------------------------------------------------------------------------------
+    def prepare(self, step_dev, sumsq_dev):
+        check(lib.vptr_optim_prepare(ptr(self.hyper), ptr(self.state), ptr(step_dev), ptr(sumsq_dev), stream()), "vptr_optim_prepare")
+
+    def adamw(self, p, g, m, v, n):
+        check(lib.vptr_adamw_ctl(ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(self.state), stream()), "vptr_adamw_ctl")

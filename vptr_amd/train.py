@@ -29,6 +29,7 @@ import torch.nn.functional as F
 from . import ops
 from ._lib import check, lib, ptr, stream
 from .model.criterion import GANLoss
+from .optim import S_GRAD_NORM, S_LR_NOW, S_SKIPPED_IN_A_ROW, S_SKIPPED_TOTAL, STATE_KEY, LRSchedule, OptimControls
 
 
 _HIP_NODE_TYPES = {0: "kernel", 1: "memcpy", 2: "memset", 3: "host", 4: "graph", 5: "empty", 6: "wait_event", 7: "event_record",
@@ -68,9 +69,19 @@ DP_CHUNKS = 4  # grouped weight-gradient launches per step when gradients are ex
 
 class FlatAdamW:
     """torch.optim.AdamW semantics (lr, betas, eps, decoupled weight decay, bias correction) on one flat slab, with
-    clip_grad_norm_ folded in.  Every parameter must receive a gradient each step (true for the VPTR transformers)."""
+    clip_grad_norm_ folded in.  Every parameter must receive a gradient each step (true for the VPTR transformers).
 
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, channel_last=()):
+    schedule (an `optim.LRSchedule`) / skip_nonfinite: either one switches the device-resident controls on (optim.py, csrc/optim.hip).
+    The hyper-parameters then live in a device record that `set_lr` / `set_weight_decay` / `set_max_grad_norm` / `set_schedule` (and an
+    assignment to `.lr`) rewrite with stream-ordered writes, so they also reach the next replay of a captured step; the rate follows the
+    schedule on the device; with skip_nonfinite a step whose gradient norm is NaN or Inf leaves the parameters, both moments and the step
+    count bit for bit as they were and is counted (`skipped()`, `skipped_in_a_row()`).  With a constant schedule the trajectory is
+    bit-identical to the uncontrolled optimizer's.  Without controls nothing changes: the same three launches, the same state_dict."""
+
+    ctl = None   # optim.OptimControls when the controls are on
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, channel_last=(), schedule=None,
+                 skip_nonfinite=False):
         """channel_last: ids of [C, ...] parameters that the kernels consume channel-last (the (C,H,W) LayerNorm affines and
         the depthwise 3x3 weights of MlpDWBN): they are STORED channel-last in the slab and exposed as a permuted view of
         their usual shape, so no per-step transposes of the parameter or its gradient remain (AdamW is elementwise, the
@@ -108,6 +119,8 @@ class FlatAdamW:
         self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
         self.step_dev = torch.zeros(1, device=dev, dtype=torch.float32)
         self.sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
+        if schedule is not None or skip_nonfinite:
+            self.ctl = OptimControls(dev, lr, betas, eps, weight_decay, max_grad_norm, schedule, skip_nonfinite)
         ops.register_flat_slab(self.flat, self.grad)  # backward kernels accumulate weight gradients in place
         # P16 planes of every nn.Linear-shaped weight of the slab (forward operand and transposed input-gradient operand), rebuilt
         # by one launch after each step: the GEMMs then stage weights by DMA instead of splitting fp32 per tile (ops.WeightPlanes)
@@ -116,6 +129,57 @@ class FlatAdamW:
         if lin:
             self.planes = ops.WeightPlanes(lin)
             ops.register_weight_planes(self.planes)
+
+    # -- hyper-parameters: plain attributes without controls; with them every change also goes into the device record ------------
+    @property
+    def lr(self):
+        return self._lr
+
+    @lr.setter
+    def lr(self, value):
+        if self.ctl is not None:
+            self.ctl.set_lr(value)
+        self._lr = value
+
+    def _need_ctl(self, what):
+        if self.ctl is None:
+            raise RuntimeError("FlatAdamW.%s needs the device-resident controls (schedule= or skip_nonfinite=True); without them the "
+                               "hyper-parameters of a captured step are frozen" % what)
+        return self.ctl
+
+    def set_lr(self, lr):
+        """the base rate the schedule multiplies; effective from the next step, eager or replayed"""
+        self._need_ctl("set_lr")
+        self.lr = lr
+
+    def set_weight_decay(self, weight_decay):
+        self._need_ctl("set_weight_decay").set_weight_decay(weight_decay)
+        self.weight_decay = weight_decay
+
+    def set_max_grad_norm(self, max_grad_norm):
+        """None: no clipping"""
+        self._need_ctl("set_max_grad_norm").set_max_grad_norm(max_grad_norm)
+        self.max_grad_norm = max_grad_norm
+
+    def set_schedule(self, schedule):
+        """replace the schedule; it is evaluated at the step count the optimizer has reached, not restarted"""
+        self._need_ctl("set_schedule").set_schedule(schedule)
+
+    @property
+    def schedule(self):
+        return self.ctl.schedule if self.ctl is not None else None
+
+    def lr_now(self):
+        """the rate of the last applied step (0-dim fp32 device view, 0 before the first step)"""
+        return self._need_ctl("lr_now").word(S_LR_NOW)
+
+    def skipped(self):
+        """steps skipped for a non-finite gradient norm so far (0-dim fp32 device view)"""
+        return self._need_ctl("skipped").word(S_SKIPPED_TOTAL)
+
+    def skipped_in_a_row(self):
+        """... since the last applied step (0-dim fp32 device view): a run that no longer recovers shows here"""
+        return self._need_ctl("skipped_in_a_row").word(S_SKIPPED_IN_A_ROW)
 
     # -- torch.optim.AdamW-compatible state (checkpoints of the reference carry `optimizer_T.state_dict()`) ------------------
     def _logical(self, slab, i):
@@ -135,6 +199,10 @@ class FlatAdamW:
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "params": list(range(len(self.params)))}
+        if self.ctl is not None:   # torch.optim.AdamW.load_state_dict carries an unknown key of a group along untouched
+            total, in_a_row = self.ctl.counters()
+            group[STATE_KEY] = {"schedule": self.ctl.schedule.to_dict(), "skip_nonfinite": self.ctl.skip_nonfinite,
+                                "skipped_total": total, "skipped_in_a_row": in_a_row}
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
@@ -162,6 +230,15 @@ class FlatAdamW:
                         raise ValueError("FlatAdamW.load_state_dict: per-parameter step counts differ (%g vs %g)" % (s_i, step))
                     step = s_i
             self.step_dev.fill_(0.0 if step is None else step)
+        if self.ctl is not None:
+            # a checkpoint of a controlled optimizer brings its schedule, skip flag and counters; one without the key (torch.optim.AdamW,
+            # an uncontrolled FlatAdamW) leaves this optimizer's own controls in place
+            saved = g0.get(STATE_KEY)
+            if saved is not None:
+                self.ctl.skip_nonfinite = bool(saved["skip_nonfinite"])
+                self.ctl.schedule = LRSchedule.from_dict(saved["schedule"])
+                self.ctl.load_counters(saved["skipped_total"], saved["skipped_in_a_row"])
+            self.ctl.write(self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, self._last_scale)
         ops.invalidate_weight_planes()   # a checkpoint load usually rewrites the parameters too (possibly through .data)
 
     def close(self):
@@ -185,6 +262,8 @@ class FlatAdamW:
 
     def grad_norm(self):
         """global L2 norm of the (scaled) gradients of the last step (device tensor), as clip_grad_norm_ returns"""
+        if self.ctl is not None:
+            return self.ctl.word(S_GRAD_NORM)
         return self.sumsq.sqrt() * self._last_scale
 
     _last_scale = 1.0
@@ -201,15 +280,24 @@ class FlatAdamW:
         else:
             self.sumsq.zero_()
             check(lib.vptr_sumsq(ptr(self.grad), n, ptr(self.sumsq), stream()), "vptr_sumsq")
-        self.step_dev.add_(1.0)
+        if self.ctl is not None:
+            # sumsq -> prepare (skip decision, step count, schedule, update scalars: one lane) -> the update reading them -> plane refresh.
+            # A skipped step still refreshes the planes: they are rebuilt from unchanged weights.
+            self.ctl.set_grad_scale(grad_scale)
+            self.ctl.prepare(self.step_dev, self.sumsq)
+        else:
+            self.step_dev.add_(1.0)
         prof = ops.profiling.opt
         if prof is not None:   # bench.py's HBM roofline pass: HIP events on the launch stream around the optimizer's streaming kernels
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record()
-        check(lib.vptr_adamw(ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v), n, self.lr, self.betas[0], self.betas[1],
-                             self.eps, self.weight_decay, ptr(self.step_dev),
-                             ptr(self.sumsq) if self.max_grad_norm is not None else None,
-                             float(self.max_grad_norm or 0.0), float(grad_scale), stream()), "vptr_adamw")
+        if self.ctl is not None:
+            self.ctl.adamw(self.flat, self.grad, self.m, self.v, n)
+        else:
+            check(lib.vptr_adamw(ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v), n, self.lr, self.betas[0], self.betas[1],
+                                 self.eps, self.weight_decay, ptr(self.step_dev),
+                                 ptr(self.sumsq) if self.max_grad_norm is not None else None,
+                                 float(self.max_grad_norm or 0.0), float(grad_scale), stream()), "vptr_adamw")
         if prof is not None:
             ev[1].record()
         if self.planes is not None:
@@ -236,12 +324,17 @@ class NARTrainer:
     """One stage-2 NAR training step; see module docstring.  `enc`/`dec` are frozen (eval), `transformer` trains."""
 
     def __init__(self, enc, dec, transformer, batch_size, lr=1e-4, max_grad_norm=1.0, lam_pc=0.1, process_group=None,
-                 bucket_mb=64, dec_weight_grads=True, disc=None, lam_gan=None, gan_mode="vanilla"):
+                 bucket_mb=64, dec_weight_grads=True, disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False):
+        """schedule / skip_nonfinite: the device-resident optimizer controls of `FlatAdamW` (optim.py), given to the transformer's optimizer
+        and, with the adversarial branch, to the discriminator's alike.  `step` then also returns "lr" and "skipped" (and "skipped_D"), and
+        `capture`, `capture_front`, `verify_graph` work as before: `trainer.opt.set_lr(...)` between replays changes the next update.  A
+        skipped step leaves parameters, moments and step count untouched; it still refreshes the weight planes (from unchanged weights),
+        still advances the dropout seed, and BatchNorm running statistics of the forward pass it belongs to have been updated already."""
         self.enc, self.dec, self.T = enc.eval(), dec.eval(), transformer
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.bucket_elems = bucket_mb * (1 << 20) // 4
-        self._init_gan(disc, lam_gan, lr, gan_mode)
+        self._init_gan(disc, lam_gan, lr, gan_mode, schedule, skip_nonfinite)
         # Stage 2 optimises the transformer only (train_NAR.py:205).  The reference nevertheless leaves the decoder's
         # parameters trainable (:190-191), so its backward computes decoder weight gradients nobody consumes; that work
         # is reproduced by default (dec_weight_grads=True) so that the measured step does everything the reference's does.
@@ -252,7 +345,8 @@ class NARTrainer:
         self.dec_weight_grads = bool(dec_weight_grads)
         for mod in list(self.enc.modules()) + list(self.dec.modules()):
             mod._vptr_frozen = True  # never stepped here: packed conv weights / eval-BN folds are cached (ops.frozen_weights)
-        self.opt = FlatAdamW(self.T.parameters(), lr=lr, max_grad_norm=max_grad_norm, channel_last=_channel_last_ids(self.T))
+        self.opt = FlatAdamW(self.T.parameters(), lr=lr, max_grad_norm=max_grad_norm, channel_last=_channel_last_ids(self.T),
+                             schedule=schedule, skip_nonfinite=skip_nonfinite)
         dev = self.opt.flat.device
         # loss_name_list MSE / GDL(alpha=1) / BiPatchNCE(N, Tf, 8, 8, temperature 1.0) of train_NAR.py:176-179 run as the fused kernels of
         # csrc/losses.hip (ops.mse_gdl, ops.nce_loss): plain kernel launches only, so the step can live in a hipGraph
@@ -271,7 +365,7 @@ class NARTrainer:
     _front_items = ()
 
     # -- optional adversarial branch (train_NAR.py:22-30,37-41,66-79; train_FAR.py:22-45,66-80): off in the reference scripts ----
-    def _init_gan(self, disc, lam_gan, lr, gan_mode):
+    def _init_gan(self, disc, lam_gan, lr, gan_mode, schedule=None, skip_nonfinite=False):
         self.disc, self.lam_gan = disc, lam_gan
         if disc is None:
             return
@@ -279,7 +373,8 @@ class NARTrainer:
             raise ValueError("a discriminator needs lam_gan (train_NAR.py:67)")
         for p in disc.parameters():
             p.requires_grad_(True)
-        self.opt_D = FlatAdamW(list(disc.parameters()), lr=lr, betas=(0.5, 0.999), weight_decay=0.0)  # Adam, :204
+        self.opt_D = FlatAdamW(list(disc.parameters()), lr=lr, betas=(0.5, 0.999), weight_decay=0.0, schedule=schedule,
+                               skip_nonfinite=skip_nonfinite)  # Adam, :204
         self.gan = GANLoss(gan_mode, target_real_label=1.0, target_fake_label=0.0).to(self.opt_D.flat.device)
 
     def _disc_update(self, fake, real):
@@ -300,7 +395,10 @@ class NARTrainer:
         self.opt_D.step()
         for p in self.disc.parameters():
             p.requires_grad_(False)
-        return {"Dtotal": loss_D.detach(), "Dfake": l_fake.detach(), "Dreal": l_real.detach()}
+        out = {"Dtotal": loss_D.detach(), "Dfake": l_fake.detach(), "Dreal": l_real.detach()}
+        if self.opt_D.ctl is not None:
+            out["skipped_D"] = self.opt_D.skipped()
+        return out
 
     # -- data-parallel gradient exchange: a few large RCCL all-reduces on the flat gradient slab ---------------------
     _grad_scale = 1.0   # factor the next optimizer step applies to the gradient slab (1 / world after a summed exchange)
@@ -470,6 +568,8 @@ class NARTrainer:
                 self._exchange_held_wgrads()
             self.opt.step(grad_scale=self._grad_scale)
             self._static_out["grad_norm"] = self.opt.grad_norm()
+            if self.opt.ctl is not None:
+                self._static_out["lr"], self._static_out["skipped"] = self.opt.lr_now(), self.opt.skipped()
             return self._static_out
         if self._graph is not None:
             # replays are stream-ordered like any other launch; tests/test_20_graph_gpu.py compares them with eager steps (the
@@ -601,6 +701,8 @@ class NARTrainer:
         self._backward_and_exchange(loss)
         self.opt.step(grad_scale=self._grad_scale)
         terms["grad_norm"] = self.opt.grad_norm()
+        if self.opt.ctl is not None:
+            terms["lr"], terms["skipped"] = self.opt.lr_now(), self.opt.skipped()
         return terms
 
     # -- validation pass: the train_flag=False branch of single_iter (train_NAR.py:88-100, train_FAR.py:85-94) ------------------------
@@ -709,10 +811,14 @@ class NARTrainer:
         dev = self.opt.flat.device
         snap = {"flat": self.opt.flat.clone(), "m": self.opt.m.clone(), "v": self.opt.v.clone(), "step": self.opt.step_dev.clone(),
                 "buffers": [b.detach().clone() for b in self.T.buffers()], "seed": ops._master_seed(dev).clone()}
+        if self.opt.ctl is not None:   # the controls' device-written record: last rate, skip counters, the update scalars
+            snap["ctl"] = self.opt.ctl.state.clone()
         if self.disc is not None:   # the adversarial branch steps a second slab and the discriminator's BatchNorm statistics
             o = self.opt_D
             snap["D"] = {"flat": o.flat.clone(), "m": o.m.clone(), "v": o.v.clone(), "step": o.step_dev.clone(),
                          "buffers": [b.detach().clone() for b in self.disc.buffers()]}
+            if o.ctl is not None:
+                snap["D"]["ctl"] = o.ctl.state.clone()
         return snap
 
     def _restore(self, snap):
@@ -722,9 +828,13 @@ class NARTrainer:
             for b, v in zip(self.T.buffers(), snap["buffers"]):
                 b.copy_(v)
             ops._master_seed(dev).copy_(snap["seed"])
+            if "ctl" in snap:
+                self.opt.ctl.state.copy_(snap["ctl"])
             if self.disc is not None:
                 o, d = self.opt_D, snap["D"]
                 o.flat.copy_(d["flat"]); o.m.copy_(d["m"]); o.v.copy_(d["v"]); o.step_dev.copy_(d["step"])
+                if "ctl" in d:
+                    o.ctl.state.copy_(d["ctl"])
                 for b, v in zip(self.disc.buffers(), d["buffers"]):
                     b.copy_(v)
                 if o.planes is not None:
@@ -808,12 +918,13 @@ class FARTrainer(NARTrainer):
     flat-slab optimizer, grouped weight gradients and data-parallel exchange with `NARTrainer`."""
 
     def __init__(self, enc, dec, transformer, lr=1e-4, max_grad_norm=1.0, process_group=None, bucket_mb=64, dec_weight_grads=True,
-                 disc=None, lam_gan=None, gan_mode="vanilla"):
+                 disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False):
+        """schedule / skip_nonfinite: as in `NARTrainer`"""
         self.enc, self.dec, self.T = enc.eval(), dec.eval(), transformer
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.bucket_elems = bucket_mb * (1 << 20) // 4
-        self._init_gan(disc, lam_gan, lr, gan_mode)
+        self._init_gan(disc, lam_gan, lr, gan_mode, schedule, skip_nonfinite)
         for p in enc.parameters():
             p.requires_grad_(False)
         for p in dec.parameters():
@@ -821,7 +932,8 @@ class FARTrainer(NARTrainer):
         self.dec_weight_grads = bool(dec_weight_grads)
         for mod in list(self.enc.modules()) + list(self.dec.modules()):
             mod._vptr_frozen = True
-        self.opt = FlatAdamW(self.T.parameters(), lr=lr, max_grad_norm=max_grad_norm, channel_last=_channel_last_ids(self.T))
+        self.opt = FlatAdamW(self.T.parameters(), lr=lr, max_grad_norm=max_grad_norm, channel_last=_channel_last_ids(self.T),
+                             schedule=schedule, skip_nonfinite=skip_nonfinite)
         self._bufsync = None   # the FAR transformer has no BatchNorm (LayerNorm conv-FFNs): nothing to broadcast per forward
         self._graph = None
 
@@ -872,13 +984,19 @@ class AETrainer:
     update: lam_gan * BCE(D(rec), 1) + MSE + GDL, Adam on Enc + Dec.  torch.optim.Adam(lr 2e-4, betas (0.5, 0.999)) is
     AdamW with weight_decay 0, so both optimizers are `FlatAdamW` slabs (no clipping in this stage)."""
 
-    def __init__(self, enc, dec, disc, lr=2e-4, lam_gan=0.01, betas=(0.5, 0.999), gan_mode="vanilla"):
+    def __init__(self, enc, dec, disc, lr=2e-4, lam_gan=0.01, betas=(0.5, 0.999), gan_mode="vanilla", schedule=None, skip_nonfinite=False):
+        """schedule / skip_nonfinite: the device-resident optimizer controls of `FlatAdamW` (optim.py) for both optimizers; `step` then
+        also returns "lr_G", "lr_D", "skipped_G", "skipped_D".  The two decisions are independent: a non-finite discriminator gradient
+        skips the discriminator's update only.  A skipped step still advances the dropout seed and the BatchNorm running statistics of
+        Enc, Dec and the discriminator, which the forward passes have written before the gradient exists: a non-finite INPUT therefore
+        still reaches the running statistics (train-mode steps do not read them; an `eval_step` does)."""
         self.enc, self.dec, self.disc = enc, dec, disc
         for m in (enc, dec, disc):
             for p in m.parameters():
                 p.requires_grad_(True)
-        self.opt_G = FlatAdamW(list(enc.parameters()) + list(dec.parameters()), lr=lr, betas=betas, weight_decay=0.0)
-        self.opt_D = FlatAdamW(list(disc.parameters()), lr=lr, betas=betas, weight_decay=0.0)
+        self.opt_G = FlatAdamW(list(enc.parameters()) + list(dec.parameters()), lr=lr, betas=betas, weight_decay=0.0, schedule=schedule,
+                               skip_nonfinite=skip_nonfinite)
+        self.opt_D = FlatAdamW(list(disc.parameters()), lr=lr, betas=betas, weight_decay=0.0, schedule=schedule, skip_nonfinite=skip_nonfinite)
         self.gan = GANLoss(gan_mode, target_real_label=1.0, target_fake_label=0.0).to(self.opt_G.flat.device)
         self.lam_gan = lam_gan
 
@@ -936,8 +1054,11 @@ class AETrainer:
         loss_G = self.lam_gan * l_gan + l_mse + l_gdl
         loss_G.backward()
         self.opt_G.step()
-        return {"AEgan": l_gan.detach(), "AE_MSE": l_mse.detach(), "AE_GDL": l_gdl.detach(), "AE_total": loss_G.detach(),
-                "Dtotal": loss_D.detach(), "Dfake": l_fake.detach(), "Dreal": l_real.detach()}
+        out = {"AEgan": l_gan.detach(), "AE_MSE": l_mse.detach(), "AE_GDL": l_gdl.detach(), "AE_total": loss_G.detach(),
+               "Dtotal": loss_D.detach(), "Dfake": l_fake.detach(), "Dreal": l_real.detach()}
+        if self.opt_G.ctl is not None:
+            out.update(lr_G=self.opt_G.lr_now(), lr_D=self.opt_D.lr_now(), skipped_G=self.opt_G.skipped(), skipped_D=self.opt_D.skipped())
+        return out
 
 
 def run_epoch(trainer, loader, train, meters, ingest=None):
