@@ -146,6 +146,11 @@ OPTIM_SIGNATURES = {
     "vptr_optim_prepare": [P, P, P, P, P],
     "vptr_adamw_ctl": [P, P, P, P, L, P, P],
 }
+# conv-FFN backward without the gradient tensor between norm2 and the depthwise 3x3, declared in include/vptr_hip_convffn.h (additive as well)
+CONVFFN_SIGNATURES = {
+    "vptr_norm_act_bwd_sums": [P, P, P, P, P, P, P, P, P, I, I, I, I, F, P, U, P, P],
+    "vptr_dwconv3x3_norm_bwd": [P, P, P, P, P, P, P, I, F, P, U, P, P, P, P, P, I, I, I, I, I, P],
+}
 
 
 def _load():
@@ -154,7 +159,7 @@ def _load():
             "vptr_amd: %s is missing. Build it with `python -m vptr_amd.build` (needs hipcc, gfx950). "
             "There is no CPU / PyTorch fallback for the VPTR hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
+    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.argtypes = argt
         fn.restype = c_int

@@ -42,7 +42,7 @@ def _compile(src, force):
     stamp = obj + ".sha"
     deps = [os.path.join(CSRC, src), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_shared.h"), os.path.join(CSRC, "attn_mfma.h"),
             os.path.join(CSRC, "attn_route.h"), os.path.join(HERE, "..", "include", "vptr_hip.h"), os.path.join(HERE, "..", "include", "vptr_hip_ext.h"),
-            os.path.join(HERE, "..", "include", "vptr_hip_optim.h")]
+            os.path.join(HERE, "..", "include", "vptr_hip_optim.h"), os.path.join(HERE, "..", "include", "vptr_hip_convffn.h")]
     dig = _digest(deps)
     if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig:
         return obj, False

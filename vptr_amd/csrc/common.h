@@ -141,6 +141,16 @@ __device__ __forceinline__ float vptr_act_grad(float h, int act) {
   return 1.f;
 }
 
+// backward helper of the normalise + activation kernels: g = dy * drop * act'(z), z = xhat*w + b
+__device__ __forceinline__ float norm_act_g(float dy, float xh, float w, float b, int act, float dscale) {
+  const float z = xh * w + b;
+  float g = dy * dscale;
+  if (act == VPTR_ACT_GELU) g *= vptr_gelu_grad(z);
+  else if (act == VPTR_ACT_RELU) g = z > 0.f ? g : 0.f;
+  else if (act == VPTR_ACT_LRELU) g = z > 0.f ? g : 0.2f * g;
+  return g;
+}
+
 // ---- wave / block reductions (wave = 64) ----------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -1,5 +1,6 @@
 // Depthwise 3x3 forward / data gradient / weight gradient and the fused norm1 + GELU + depthwise forward of the conv-FFN (gfx950).
 #include "common.h"
+#include "../../include/vptr_hip_convffn.h"
 #include <type_traits>
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -420,6 +421,192 @@ extern "C" int vptr_dwconv3x3_norm_fwd(const float* x, const float* raw_stats, c
   const int64_t total = (int64_t)frames * W2 * (F / 4);
   dwconv_norm_fwd3_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
       x, raw_stats, aff_w, aff_b, eps, act, w9, b, y, reinterpret_cast<_Float16*>(a_half), mean_out, rstd_out, frames, H, W, F / 4, frame_stats);
+  VPTR_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Backward mirror of dwconv_norm_lds_kernel (include/vptr_hip_convffn.h): the dx arithmetic of the conv-FFN's SECOND normalisation applied in the
+// load path of the depthwise gradients.  g2 = d loss / d y2 (y2 = the depthwise output) is computed once per element into an LDS slab and never
+// written to memory; the data gradient da, the weight gradient dw9 and the bias gradient db are taken from the slab.  Per conv-FFN at the K64
+// step's shape (u = 86.5 MB): dy, y2 and the fp16 side copy read once, da written once = 3.5 u, against 6.5 u of the three launches it replaces
+// (norm_act_bwd_dx4_pos_kernel: 2 u + u, dwconv_fwd3_kernel flip = 1: u + u, dwconv_bwd_w_kernel<true, true, 16>: 1.5 u).
+// ---------------------------------------------------------------------------------------------------------------
+// phase-1 arithmetic on one channel quad: the dx of out = dropout(act(xhat * w + b)) w.r.t. x, expression by expression that of
+// norm_act_bwd_dx4_pos_kernel (e0: flat element index of the quad's first channel = the dropout counter)
+__device__ __forceinline__ float4 norm_act_dx4(const float4 dv, const float4 xv, const float4 ww, const float4 bb, const float mu, const float rs,
+                                               const float t1, const float t2, const float inv_n, const int act, const bool drop, const float p,
+                                               const uint64_t seed, const uint32_t site, const uint64_t e0) {
+  const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ds4[4] = {dv.x, dv.y, dv.z, dv.w};
+  const float wv[4] = {ww.x, ww.y, ww.z, ww.w}, bv[4] = {bb.x, bb.y, bb.z, bb.w};
+  float o[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const float xh = (xs[u] - mu) * rs;
+    const float dsc = drop ? vptr_drop_scale(seed, site, e0 + u, p) : 1.f;
+    const float g = norm_act_g(ds4[u], xh, wv[u], bv[u], act, dsc);
+    o[u] = rs * (g * wv[u] - t1 * inv_n - xh * t2 * inv_n);
+  }
+  return make_float4(o[0], o[1], o[2], o[3]);
+}
+// One workgroup = 64 channels (16 quads) x the H * W <= 64 pixels of a frame, over `fpb` consecutive frames: thread = (quad, pixel lane), four
+// pixel slots p0 + 16 k.  Per frame: phase 1 turns the slots' (dy, y2) into g2 and stores it into the slab -- [(H + 2) x (W + 2) pixels][16 quads]
+// float4 with a border of zeros written once, so the taps need neither clamps nor masks --; the loads of the NEXT frame are issued before it
+// and stay in flight under phase 1 and the tap phase.  Taps: with v_t = g2[q + off_t] for the thread's own pixel q,
+//   da[q] = sum_t w9[8 - t] * v_t     and     dw9[8 - t] += a[q] * v_t     (dw9[t] = sum_p g2[p] a[p + off_t], re-indexed by q = p + off_t),
+// so one set of nine LDS reads serves both gradients and the fp16 activation is only needed at the thread's own pixels (registers, no LDS image);
+// the bias gradient is the centre tap.  The weight / bias sums stay in registers over the frames, are reduced over the wave's four pixel lanes
+// with shuffles and over the four waves through the slab, and leave as one atomic per (tap or bias, channel) and workgroup.
+// ACT / DROP: the activation (VPTR_ACT_GELU, or -1 = the run-time `act_rt`) and p > 0 as compile-time values -- with the tests inside the
+// per-element arithmetic every one of a thread's 16 elements sat in basic blocks of its own and their rcp / exp chains ran one after the other.
+template <int ACT, bool DROP>
+__global__ __launch_bounds__(256) void dwconv_norm_bwd_lds_kernel(const float4* __restrict__ dy, const float4* __restrict__ y2,
+                                                                  const float* __restrict__ mean2, const float* __restrict__ rstd2,
+                                                                  const float4* __restrict__ w2, const float4* __restrict__ b2,
+                                                                  const float* __restrict__ fsum, int act_rt, float p,
+                                                                  const uint64_t* __restrict__ seed_dev, uint32_t site,
+                                                                  const half4_t* __restrict__ ah, const float4* __restrict__ w9,
+                                                                  float4* __restrict__ da, float* __restrict__ dw9, float* __restrict__ db,
+                                                                  int frames, int H, int W, int F4, int fpb) {
+  extern __shared__ float4 dwb_tile[];   // [(H + 2) * (W + 2) + 1][16] (the last pixel: where dead pixel slots write), at least 10 KB (the final reduction)
+  const int act = ACT >= 0 ? ACT : act_rt;
+  const int tid = threadIdx.x, c4l = tid & 15, p0 = tid >> 4;
+  const int c4 = blockIdx.x * 16 + c4l;
+  const int HW = H * W, Wp = W + 2, P = HW * F4;
+  const int f0 = blockIdx.y * fpb, f1 = min(frames, f0 + fpb);
+  uint64_t seed = 0;
+  if (DROP) seed = *seed_dev;
+  const float inv_n = 1.f / (float)((int64_t)HW * F4 * 4);
+  for (int i = tid; i < (H + 2) * Wp * 16; i += 256) dwb_tile[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  // the four pixel slots: position inside a frame (float4 units; clamped into the frame), centre in the slab, the affine tables
+  int pos[4], ctr[4], dst[4];
+  bool ok[4];
+  float4 wv[4], bv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int pk = p0 + 16 * k;
+    ok[k] = pk < HW;
+    const int pc = min(pk, HW - 1), py = pc / W, px = pc - py * W;
+    pos[k] = pc * F4 + c4;
+    ctr[k] = ((py + 1) * Wp + px + 1) * 16 + c4l;
+    dst[k] = ok[k] ? ctr[k] : (H + 2) * Wp * 16 + c4l;   // phase 1 runs without branches: a dead slot recomputes the last pixel into the spare one
+    wv[k] = w2[pos[k]];
+    bv[k] = b2[pos[k]];
+  }
+  float4 wf[9], acc[9], ab = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    wf[t] = w9[(int64_t)(8 - t) * F4 + c4];
+    acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float4 dv[4], yv[4];
+  half4_t av[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t i = (int64_t)f0 * P + pos[k];
+    dv[k] = dy[i];
+    yv[k] = y2[i];
+    av[k] = ah[i];
+  }
+  __syncthreads();   // the border is in place
+  for (int f = f0; f < f1; ++f) {
+    const float mu = mean2[f], rs = rstd2[f], t1 = fsum[f], t2 = fsum[frames + f];
+    const int64_t base = (int64_t)f * P;
+    // the next frame's operands, requested BEFORE this frame's arithmetic: a frame's loads have a whole frame of work (phase 1 and the taps) to
+    // arrive under (the last frame asks for itself again: no branch, no out-of-range address)
+    const int64_t nbase = (int64_t)min(f + 1, f1 - 1) * P;
+    float4 nd[4], ny[4];
+    half4_t na[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      nd[k] = dy[nbase + pos[k]];
+      ny[k] = y2[nbase + pos[k]];
+      na[k] = ah[nbase + pos[k]];
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keep the requests ahead of phase 1 (the scheduler would sink them to shorten their live ranges)
+    // ---- phase 1: g2 of the four slots into the slab
+    half4_t a[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      dwb_tile[dst[k]] = norm_act_dx4(dv[k], yv[k], wv[k], bv[k], mu, rs, t1, t2, inv_n, act, DROP, p, seed, site, (uint64_t)(base + pos[k]) * 4);
+      a[k] = av[k];
+    }
+    __syncthreads();
+    // ---- taps: nine slab reads per pixel for da, dw9 and db
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!ok[k]) continue;
+      const float4 af = make_float4((float)a[k].x, (float)a[k].y, (float)a[k].z, (float)a[k].w);
+      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const float4 v = dwb_tile[ctr[k] + ((ky - 1) * Wp + (kx - 1)) * 16];
+          fma4(o, wf[ky * 3 + kx], v);
+          fma4(acc[ky * 3 + kx], af, v);
+          if (ky == 1 && kx == 1) { ab.x += v.x; ab.y += v.y; ab.z += v.z; ab.w += v.w; }
+        }
+      da[base + pos[k]] = o;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { dv[k] = nd[k]; yv[k] = ny[k]; av[k] = na[k]; }
+    __syncthreads();   // every tap of this frame is read before the next frame's phase 1 (or the reduction below) overwrites the slab
+  }
+  // ---- the sums: over the wave's four pixel lanes (lanes l, l ^ 16, l ^ 32, l ^ 48 hold one channel quad), then over the four waves
+  auto lanes4 = [](float4& v) {
+    v.x += __shfl_xor(v.x, 16, 64); v.y += __shfl_xor(v.y, 16, 64); v.z += __shfl_xor(v.z, 16, 64); v.w += __shfl_xor(v.w, 16, 64);
+    v.x += __shfl_xor(v.x, 32, 64); v.y += __shfl_xor(v.y, 32, 64); v.z += __shfl_xor(v.z, 32, 64); v.w += __shfl_xor(v.w, 32, 64);
+  };
+#pragma unroll
+  for (int t = 0; t < 9; ++t) lanes4(acc[t]);
+  lanes4(ab);
+  const int wave = tid >> 6;
+  if ((tid & 63) < 16) {   // [wave][9 taps + bias][16 quads] float4
+#pragma unroll
+    for (int t = 0; t < 9; ++t) dwb_tile[(wave * 10 + t) * 16 + c4l] = acc[t];
+    dwb_tile[(wave * 10 + 9) * 16 + c4l] = ab;
+  }
+  __syncthreads();
+  const float* red = reinterpret_cast<const float*>(dwb_tile);
+  const int F = F4 * 4;
+  for (int o = tid; o < 640; o += 256) {
+    const int r = o >> 6, ch = o & 63;
+    const float sum = (red[r * 64 + ch] + red[(10 + r) * 64 + ch]) + (red[(20 + r) * 64 + ch] + red[(30 + r) * 64 + ch]);
+    if (r < 9) unsafeAtomicAdd(dw9 + (int64_t)(8 - r) * F + blockIdx.x * 64 + ch, sum);   // acc[t] belongs to tap 8 - t
+    else unsafeAtomicAdd(db + blockIdx.x * 64 + ch, sum);
+  }
+}
+extern "C" int vptr_dwconv3x3_norm_bwd(const float* dy, const float* y2, const float* mean2, const float* rstd2, const float* w2, const float* b2,
+                                       const float* fsum, int act, float dropout_p, const uint64_t* seed_dev, uint32_t site, const void* a_half,
+                                       const float* w9, float* da, float* dw9, float* db, int frames, int H, int W, int F, int frames_per_group,
+                                       vptr_stream_t stream) {
+  VPTR_CHECK(dy && y2 && mean2 && rstd2 && w2 && b2 && fsum && a_half && w9 && da && dw9 && db && frames > 0 && H > 0 && W > 0 && F > 0 &&
+                 frames_per_group >= 0,
+             "dwconv3x3_norm_bwd: bad arguments");
+  VPTR_CHECK(!g_vptr_deterministic, "dwconv3x3_norm_bwd: workgroups meet in atomics; the deterministic mode takes vptr_norm_act_bwd + vptr_dwconv3x3_bwd_xh");
+  const int W2 = W / 2;
+  VPTR_CHECK(F % 64 == 0 && W % 2 == 0 && W2 >= 1 && 16 % W2 == 0 && (W2 * (F / 4)) % 64 == 0,
+             "dwconv3x3_norm_bwd: needs F %% 64 == 0, W even, W / 2 dividing 16 and (W/2)*(F/4) %% 64 == 0 (got W %d, F %d)", W, F);
+  VPTR_CHECK((int64_t)H * W <= 64, "dwconv3x3_norm_bwd: maps of at most 64 pixels (got %d x %d)", H, W);
+  VPTR_CHECK(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || seed_dev), "dwconv3x3_norm_bwd: dropout needs 0 <= p < 1 and seed_dev");
+  VPTR_CHECK(((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y2) | reinterpret_cast<uintptr_t>(w2) | reinterpret_cast<uintptr_t>(b2) |
+               reinterpret_cast<uintptr_t>(w9) | reinterpret_cast<uintptr_t>(da)) & 15) == 0 && (reinterpret_cast<uintptr_t>(a_half) & 7) == 0,
+             "dwconv3x3_norm_bwd: operands must be 16-byte aligned (the fp16 operand: 8)");
+  int fpb = frames_per_group;
+  // as dwconv_bwd_w_kernel: 8 frames per workgroup on long clips (K64 shape, 2 / 4 / 8 frames per workgroup: 89 / 80 / 76 us per launch --
+  // the first frame of a group is the one whose loads nothing hides, profiles/convffn_bwd_fused_kernel_stats.md)
+  if (fpb == 0) fpb = frames >= 64 ? 8 : 1;
+  VPTR_CHECK(frames <= 65535 * (int64_t)fpb, "dwconv3x3_norm_bwd: more than 65535 frame groups");
+  const size_t slab = ((size_t)(H + 2) * (W + 2) + 1) * 256;   // <= (34 * 4 + 1) * 256 = 35 072 B on maps of at most 64 pixels
+  const size_t lds = slab > 10240 ? slab : 10240;
+  const bool gelu = act == VPTR_ACT_GELU, drop = dropout_p > 0.f;
+  auto kern = gelu ? (drop ? dwconv_norm_bwd_lds_kernel<VPTR_ACT_GELU, true> : dwconv_norm_bwd_lds_kernel<VPTR_ACT_GELU, false>)
+                   : (drop ? dwconv_norm_bwd_lds_kernel<-1, true> : dwconv_norm_bwd_lds_kernel<-1, false>);
+  kern<<<dim3(F / 64, cdiv(frames, fpb)), 256, lds, (hipStream_t)stream>>>(
+      reinterpret_cast<const float4*>(dy), reinterpret_cast<const float4*>(y2), mean2, rstd2, reinterpret_cast<const float4*>(w2),
+      reinterpret_cast<const float4*>(b2), fsum, act, dropout_p, seed_dev, site, reinterpret_cast<const half4_t*>(a_half),
+      reinterpret_cast<const float4*>(w9), reinterpret_cast<float4*>(da), dw9, db, frames, H, W, F / 4, fpb);
   VPTR_LAUNCH_CHECK();
   return 0;
 }

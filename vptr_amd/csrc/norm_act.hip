@@ -2,6 +2,7 @@
 // All kernels here are HBM-bound: float4 accesses, thread-per-column sweeps with coalesced row reads for column reductions
 // (partials combined with fp32 atomics or left per workgroup for vptr_partial_reduce).
 #include "common.h"
+#include "../../include/vptr_hip_convffn.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // conv-FFN statistics.  colstats: per-channel mean / biased variance over all rows (BatchNorm2d batch stats).
@@ -325,15 +326,7 @@ extern "C" int vptr_norm_act_fwd(const float* x, float* mean, float* rstd, const
   return 0;
 }
 
-// backward helper: g = dy * drop * act'(z), z = xhat*w + b
-__device__ __forceinline__ float norm_act_g(float dy, float xh, float w, float b, int act, float dscale) {
-  const float z = xh * w + b;
-  float g = dy * dscale;
-  if (act == VPTR_ACT_GELU) g *= vptr_gelu_grad(z);
-  else if (act == VPTR_ACT_RELU) g = z > 0.f ? g : 0.f;
-  else if (act == VPTR_ACT_LRELU) g = z > 0.f ? g : 0.2f * g;
-  return g;
-}
+// (norm_act_g, the backward helper g = dy * drop * act'(z), lives in common.h: dwconv.hip applies it as well)
 
 // phase 1, per-column statistics (BN): dw[c] += sum g*xhat, db[c] += sum g.  (s1 = w*db, s2 = w*dw afterwards.)
 __global__ __launch_bounds__(256) void norm_act_bwd_col_reduce(const float* __restrict__ dy, const float* __restrict__ x,
@@ -692,6 +685,29 @@ extern "C" int vptr_norm_act_bwd_partials(int rows, int F, int HW, int per_col) 
   const int fpb = (frames + want - 1) / want;
   return (frames + fpb - 1) / fpb;   // chunks of fpb frames (<= want)
 }
+// phases 1 and 1c of the LayerNorm((F,H,W)) backward: affine gradients (dw / db atomics, or the deferred `partials` rows) and the frame sums
+// s1[f], s2[f] left in scratch[0 .. 2 * frames) -- shared by norm_act_bwd_impl and vptr_norm_act_bwd_sums
+static int norm_act_bwd_ln_sums(const float* dy, const float* x, const float* mean, const float* rstd, const float* w, const float* b,
+                                float* dw, float* db, float* scratch, int rows, int F, int HW, int act, float dropout_p,
+                                const uint64_t* seed_dev, uint32_t site, const float* rowscale, int rs_div, int rs_mod, float* partials,
+                                hipStream_t st) {
+  VPTR_CHECK(rows % HW == 0, "norm_act_bwd: rows must be a multiple of HW");
+  const int frames = rows / HW;
+  VPTR_CHECK(F % 4 == 0, "norm_act_bwd: F must be a multiple of 4");
+  const int E4 = HW * F / 4;
+  const int ysplit = partials ? vptr_norm_act_bwd_partials(rows, F, HW, 0) : 0;
+  if (partials) VPTR_CHECK(ysplit > 0 && (reinterpret_cast<uintptr_t>(partials) & 15) == 0, "norm_act_bwd: no deferred variant for this geometry");
+  // deferred: no atomics, so the frames are cut into more chunks (more waves in flight, 2 - 5 frames per wave instead of 10)
+  const int fpb = partials ? (frames + ysplit - 1) / ysplit : ((frames >= 64 && !g_vptr_deterministic) ? (frames + 3) / 4 : frames);   // no partial buffer + deterministic: one adder per element
+  if (partials) VPTR_CHECK(cdiv(frames, fpb) == ysplit, "norm_act_bwd: frames %d do not split into %d chunks", frames, ysplit);   // (holds by construction)
+  const int nparts = cdiv(E4, 64);  // scratch: [2*frames] sums followed by [nparts, frames, 2] per-wave partials
+  float* part = scratch + 2 * frames;
+  norm_act_bwd_frame_affine<<<dim3(nparts, cdiv(frames, fpb)), 256, 0, st>>>(dy, x, mean, rstd, w, b, dw, db, part, E4, F, HW, act,
+                                                                                   dropout_p, seed_dev, site, frames, fpb, rowscale,
+                                                                                   rs_div, rs_mod, partials);
+  norm_act_bwd_frame_final<<<frames, 256, 0, st>>>(part, scratch, nparts, frames);
+  return 0;
+}
 static int norm_act_bwd_impl(const float* dy, const float* x, const float* mean, const float* rstd, const float* w,
                              const float* b, float* dx, float* dw, float* db, float* scratch, int rows, int F, int HW,
                              int per_col, int act, int const_stats, float dropout_p, const uint64_t* seed_dev,
@@ -725,21 +741,10 @@ static int norm_act_bwd_impl(const float* dy, const float* x, const float* mean,
                                                          seed_dev, site, F, const_stats, rowscale, rs_div, rs_mod);
     accum2_kernel<<<cdiv(F, 256), 256, 0, st>>>(scratch, dw, db, F);
   } else {
-    VPTR_CHECK(rows % HW == 0, "norm_act_bwd: rows must be a multiple of HW");
+    if (const int rc = norm_act_bwd_ln_sums(dy, x, mean, rstd, w, b, dw, db, scratch, rows, F, HW, act, dropout_p, seed_dev, site, rowscale,
+                                            rs_div, rs_mod, partials, st))
+      return rc;
     const int frames = rows / HW;
-    VPTR_CHECK(F % 4 == 0, "norm_act_bwd: F must be a multiple of 4");
-    const int E4 = HW * F / 4;
-    const int ysplit = partials ? vptr_norm_act_bwd_partials(rows, F, HW, 0) : 0;
-    if (partials) VPTR_CHECK(ysplit > 0 && (reinterpret_cast<uintptr_t>(partials) & 15) == 0, "norm_act_bwd: no deferred variant for this geometry");
-    // deferred: no atomics, so the frames are cut into more chunks (more waves in flight, 2 - 5 frames per wave instead of 10)
-    const int fpb = partials ? (frames + ysplit - 1) / ysplit : ((frames >= 64 && !g_vptr_deterministic) ? (frames + 3) / 4 : frames);   // no partial buffer + deterministic: one adder per element
-    if (partials) VPTR_CHECK(cdiv(frames, fpb) == ysplit, "norm_act_bwd: frames %d do not split into %d chunks", frames, ysplit);   // (holds by construction)
-    const int nparts = cdiv(E4, 64);  // scratch: [2*frames] sums followed by [nparts, frames, 2] per-wave partials
-    float* part = scratch + 2 * frames;
-    norm_act_bwd_frame_affine<<<dim3(nparts, cdiv(frames, fpb)), 256, 0, st>>>(dy, x, mean, rstd, w, b, dw, db, part, E4, F, HW, act,
-                                                                                     dropout_p, seed_dev, site, frames, fpb, rowscale,
-                                                                                     rs_div, rs_mod, partials);
-    norm_act_bwd_frame_final<<<frames, 256, 0, st>>>(part, scratch, nparts, frames);
     if (vec4 && frames >= 16 && (int64_t)rows * (F / 4) >= (1 << 18))
       norm_act_bwd_dx4_pos_kernel<<<dim3(cdiv(HW * (F / 4), 256), (frames / 4 < 1 ? 1 : (frames / 4 > 65535 ? 65535 : frames / 4))), 256, 0, st>>>(
           reinterpret_cast<const float4*>(dy), reinterpret_cast<const float4*>(x), mean, rstd, w, b, scratch, dx, frames, F / 4, HW, act, dropout_p,
@@ -769,4 +774,19 @@ extern "C" int vptr_norm_act_bwd_deferred(const float* dy, const float* x, const
   VPTR_CHECK(partials != nullptr, "norm_act_bwd_deferred: null partial-sum buffer");
   return norm_act_bwd_impl(dy, x, mean, rstd, w, b, dx, nullptr, nullptr, scratch, rows, F, HW, 0, act, const_stats, dropout_p, seed_dev, site,
                            rowscale, rs_div, rs_mod, p16, partials, stream);
+}
+// Phases 1 and 1c of vptr_norm_act_bwd / _deferred in LayerNorm((F,H,W)) mode WITHOUT the dx pass (include/vptr_hip_convffn.h): the caller's own
+// kernel (vptr_dwconv3x3_norm_bwd) applies the dx arithmetic to the frame sums this call leaves in scratch[0 .. 2 * frames).
+extern "C" int vptr_norm_act_bwd_sums(const float* dy, const float* x, const float* mean, const float* rstd, const float* w, const float* b,
+                                      float* dw, float* db, float* scratch, int rows, int F, int HW, int act, float dropout_p,
+                                      const uint64_t* seed_dev, uint32_t site, float* partials, vptr_stream_t stream) {
+  VPTR_CHECK(dy && x && mean && rstd && w && b && rows > 0 && F > 0 && HW >= 1 && scratch && (partials || (dw && db)), "norm_act_bwd_sums: bad arguments");
+  if (dropout_p > 0.f) VPTR_CHECK(seed_dev && dropout_p < 1.f, "norm_act_bwd_sums: dropout needs seed_dev");
+  VPTR_CHECK(((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(b)) & 15) == 0,
+             "norm_act_bwd_sums: operands must be 16-byte aligned");
+  if (const int rc = norm_act_bwd_ln_sums(dy, x, mean, rstd, w, b, dw, db, scratch, rows, F, HW, act, dropout_p, seed_dev, site, nullptr, 1, 1,
+                                          partials, (hipStream_t)stream))
+    return rc;
+  VPTR_LAUNCH_CHECK();
+  return 0;
 }

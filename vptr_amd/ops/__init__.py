@@ -42,7 +42,7 @@ from .attention import (  # noqa: F401
 )
 from .convffn import (  # noqa: F401
     _norm_act_backward, _NormActFn, _NormActFn_apply, norm_act, _DWConvFn, _DWConvFn_apply, dwconv3x3, norm_dwconv_ok, _NormDWConvFn,
-    _NormDWConvFn_apply, norm_dwconv3x3,
+    _NormDWConvFn_apply, norm_dwconv3x3, norm_dwconv_bwd_ok, _NormDWConvNormFn, _NormDWConvNormFn_apply, norm_dwconv3x3_norm,
 )
 from .layout import (  # noqa: F401
     _WindowCopyFn, _WindowCopyFn_apply, pad_tokens, crop_tokens, _ToTokensFn, _ToTokensFn_apply, _FromTokensFn, _FromTokensFn_apply,

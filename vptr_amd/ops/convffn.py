@@ -12,18 +12,29 @@ from .linear import frame_stats_ok
 # ------------------------------------------------------------------------------------------------------------------
 # conv-FFN pieces
 # ------------------------------------------------------------------------------------------------------------------
-def _norm_act_backward(dy, x, w, b, mean, rstd, rowscale, HW, per_col, act, const_stats, p, seed, site, rs_div, rs_mod, dx_p16):
+def _norm_act_backward(dy, x, w, b, mean, rstd, rowscale, HW, per_col, act, const_stats, p, seed, site, rs_div, rs_mod, dx_p16, sums_only=False):
     """backward of y = dropout(act(norm(x) * w + b)) (* rowscale): (dx, dw, db); dw / db are None when the affine gradients were accumulated
-    in place (flat gradient slab) -- directly or through the backward pass's deferred partial-sum reduction"""
+    in place (flat gradient slab) -- directly or through the backward pass's deferred partial-sum reduction.
+    sums_only (LayerNorm((F,H,W)) mode without a row scale): no dx pass -- the first result is the scratch buffer whose head holds the frame
+    sums s1[f], s2[f] for the kernel that applies the dx arithmetic itself (vptr_dwconv3x3_norm_bwd)"""
     rows, F = x.shape
-    dx = torch.empty_like(x)
+    dx = None if sums_only else torch.empty_like(x)
     sw, sb = flat_grad_for(w), flat_grad_for(b)   # accumulate straight into the flat gradient slab when both live there
     in_slab = sw is not None and sb is not None
     dw, db = (sw, sb) if in_slab else (_bw_zeros(w.shape, w.device), _bw_zeros(b.shape, b.device))
     frames = rows // HW
     scratch = torch.empty((max(2 * F, 2 * frames * (1 + 4 * ((HW * F // 4 + 255) // 256))),), device=x.device, dtype=torch.float32)
     nparts = lib.vptr_norm_act_bwd_partials(rows, F, HW, int(per_col)) if (in_slab and config.defer_ln_param_grads) else 0
-    if nparts > 0:
+    if sums_only:
+        if per_col or rowscale is not None or const_stats:
+            raise RuntimeError("norm_act backward: the sums-only form belongs to the LayerNorm((F,H,W)) mode without a row scale")
+        part = torch.empty((nparts, 2, HW * F), device=x.device, dtype=torch.float32) if nparts > 0 else None
+        check(lib.vptr_norm_act_bwd_sums(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(w), ptr(b), ptr(dw), ptr(db), ptr(scratch), rows, F, HW, act, p,
+                                         ptr(seed), site, ptr(part), stream()), "vptr_norm_act_bwd_sums")
+        if nparts > 0:
+            defer_partial_reduce(part, sw, sb, nparts, HW * F)
+        dx = scratch
+    elif nparts > 0:
         # affine gradients with an in-place destination: per-chunk partial sums, added by the backward pass's one reduction launch
         part = torch.empty((nparts, 2, HW * F), device=x.device, dtype=torch.float32)
         check(lib.vptr_norm_act_bwd_deferred(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(w), ptr(b), ptr(dx), ptr(scratch), rows, F, HW,
@@ -167,6 +178,18 @@ def norm_dwconv_ok(rows, HW, F, H, W):
             and H * W == HW)
 
 
+def norm_dwconv_bwd_ok(HW, F, H, W):
+    """where norm_dwconv_ok() holds: can the backward pass between norm2 and the depthwise 3x3 run as vptr_norm_act_bwd_sums +
+    vptr_dwconv3x3_norm_bwd (the gradient w.r.t. the depthwise output never written)?  Geometry of that kernel; the deterministic mode keeps the
+    three launches (the kernel's workgroups meet in atomics); config.fused_convffn_bwd = False switches the route off (tests, A/B by hand)."""
+    W2 = W // 2
+    return (config.fused_convffn_bwd and not config.deterministic and H * W == HW and HW <= 64 and F % 64 == 0 and W % 2 == 0 and W2 >= 1
+            and 16 % W2 == 0 and (W2 * (F // 4)) % 64 == 0)
+
+
+fused_bwd_calls = 0   # backward passes that took vptr_dwconv3x3_norm_bwd (tests assert on the route with it)
+
+
 class _NormDWConvFn(torch.autograd.Function):
     """y = dw3x3(act(LayerNorm((F,H,W))(x))) with the normalisation + activation applied in the depthwise kernel's load path
     (VidHRFormer_modules.py:430-434).  x: fc1's raw output, raw_stats: its per-frame sums (fc1's epilogue).  The activated tensor is kept
@@ -207,6 +230,76 @@ class _NormDWConvFn(torch.autograd.Function):
 
 
 _NormDWConvFn_apply = _direct_apply(_NormDWConvFn)
+
+
+class _NormDWConvNormFn(torch.autograd.Function):
+    """out = dropout(act2(norm2(dw3x3(act1(norm1(x)))))) with both LayerNorm((F,H,W)): _NormDWConvFn and norm2's _NormActFn as ONE node, so that
+    the backward pass can skip the gradient w.r.t. the depthwise output.  Forward: the two launches of the two-node form, unchanged.
+    Backward: norm2's affine gradients and frame sums (vptr_norm_act_bwd_sums), then norm2's dx arithmetic in the load path of the depthwise
+    data / weight / bias gradients (vptr_dwconv3x3_norm_bwd), then norm1's ordinary backward on (da, x).  With config.fused_convffn_bwd off or the
+    deterministic mode on AT BACKWARD TIME the node runs the three launches of the two-node form instead."""
+
+    @staticmethod
+    def forward(ctx, x, aw, ab, w9, b9, w2, b2, frames, H, W, raw_stats, frame_stats, act1, eps1, act2, eps2, p, site, out_p16, dx_p16):
+        x, aw, ab, w9, w2, b2 = _c(x), _c(aw), _c(ab), _c(w9), _c(w2), _c(b2)
+        rows, F = x.shape
+        dev = x.device
+        y2 = torch.empty_like(x)
+        ah = torch.empty((rows, F), device=dev, dtype=torch.float16) if any(ctx.needs_input_grad) else None   # no-grad forward: not written
+        mean1 = torch.empty((frames,), device=dev, dtype=torch.float32)
+        rstd1, mean2, rstd2 = torch.empty_like(mean1), torch.empty_like(mean1), torch.empty_like(mean1)
+        check(lib.vptr_dwconv3x3_norm_fwd(ptr(x), ptr(raw_stats), ptr(aw), ptr(ab), eps1, act1, ptr(w9), ptr(b9), ptr(y2), ptr(ah), ptr(mean1), ptr(rstd1),
+                                          frames, H, W, F, ptr(frame_stats), stream()), "vptr_dwconv3x3_norm_fwd")
+        out = torch.empty_like(x)
+        ctx.seed = seed_tensor(dev) if p > 0 else None
+        check(lib.vptr_norm_act_fwd(ptr(y2), ptr(mean2), ptr(rstd2), ptr(w2), ptr(b2), ptr(out), rows, F, H * W, 0, act2, p, ptr(ctx.seed), site,
+                                    None, 1, 1, None, int(out_p16), ptr(frame_stats), eps2, stream()), "vptr_norm_act_fwd")
+        ctx.save_for_backward(x, aw, ab, w9, mean1, rstd1, ah, y2, w2, b2, mean2, rstd2)
+        ctx.cfg = (frames, H, W, act1, act2, p, site, dx_p16)
+        ctx.bias_ref = b9.detach() if b9 is not None else None
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        global fused_bwd_calls
+        x, aw, ab, w9, mean1, rstd1, ah, y2, w2, b2, mean2, rstd2 = ctx.saved_tensors
+        frames, H, W, act1, act2, p, site, dx_p16 = ctx.cfg
+        dy = _c(dy)
+        F = x.shape[1]
+        # the switches are read again here: a node built before set_deterministic(True) / fused_convffn_bwd = False takes the three launches
+        fused = config.fused_convffn_bwd and not config.deterministic
+        g2, dw2, db2 = _norm_act_backward(dy, y2, w2, b2, mean2, rstd2, None, H * W, False, act2, False, p, ctx.seed, site, 1, 1, False, sums_only=fused)
+        da = torch.empty_like(x)
+        sw, sb = flat_grad_for(w9), flat_grad_for(ctx.bias_ref)
+        in_slab = sw is not None and sb is not None
+        dw9 = sw if in_slab else _bw_zeros(w9.shape, w9.device)
+        db9 = sb if in_slab else _bw_zeros((F,), x.device)
+        if fused:   # g2: the frame sums only
+            check(lib.vptr_dwconv3x3_norm_bwd(ptr(dy), ptr(y2), ptr(mean2), ptr(rstd2), ptr(w2), ptr(b2), ptr(g2), act2, p, ptr(ctx.seed), site, ptr(ah),
+                                              ptr(w9), ptr(da), ptr(dw9), ptr(db9), frames, H, W, F, 0, stream()), "vptr_dwconv3x3_norm_bwd")
+            fused_bwd_calls += 1
+        else:
+            check(lib.vptr_dwconv3x3_bwd_xh(ptr(g2), ptr(ah), ptr(w9), ptr(da), ptr(dw9), ptr(db9), frames, H, W, F, stream()), "vptr_dwconv3x3_bwd_xh")
+        if in_slab:
+            dw9 = db9 = None
+        dx, daw, dab = _norm_act_backward(da, x, aw, ab, mean1, rstd1, None, H * W, False, act1, False, 0.0, None, 0, 1, 1, dx_p16)
+        return dx, daw, dab, dw9, db9, dw2, db2, None, None, None, None, None, None, None, None, None, None, None, None, None
+
+
+_NormDWConvNormFn_apply = _direct_apply(_NormDWConvNormFn)
+
+
+def norm_dwconv3x3_norm(x, aff_w, aff_b, weight, bias, aff_w2, aff_b2, frames, H, W, raw_stats, frame_stats, act=ACT_GELU, eps=1e-5, act2=ACT_GELU,
+                        eps2=1e-5, dropout_p=0.0, site=0, out_p16=False, dx_p16=False):
+    """norm_dwconv3x3 followed by norm_act(..., "ln", raw_stats=frame_stats) as one autograd node (where norm_dwconv_ok() and norm_dwconv_bwd_ok()
+    hold): same forward launches, a backward pass without the gradient tensor between the two.  aff_w2 / aff_b2: norm2's affine, channel-last
+    [H*W, F]; frame_stats (required): the depthwise kernel accumulates norm2's per-frame sums there."""
+    if frame_stats is None or raw_stats is None:
+        raise RuntimeError("norm_dwconv3x3_norm: both normalisations take their statistics from their producers' per-frame sums")
+    F = x.shape[1]
+    w9 = weight.reshape(F, 9).t().contiguous()
+    return _NormDWConvNormFn_apply(x, aff_w, aff_b, w9, bias, aff_w2, aff_b2, int(frames), int(H), int(W), raw_stats, frame_stats, int(act), float(eps),
+                                   int(act2), float(eps2), float(dropout_p), int(site), bool(out_p16), bool(dx_p16))
 
 
 def norm_dwconv3x3(x, aff_w, aff_b, weight, bias, frames, H, W, raw_stats, frame_stats=None, act=ACT_GELU, eps=1e-5, dx_p16=False):

@@ -47,6 +47,9 @@ class _Config:
     winograd_fuse = os.environ.get("VPTR_WINO_FUSE", "1") != "0"   # output transform + next input transform in one pass through LDS
     # conv-FFN norm1 + act1 inside the depthwise kernel's load path (round 6): 0 off, 1 where it pays (ops.norm_dwconv_ok), 2 wherever valid
     fused_norm_dwconv_mode = int(os.environ.get("VPTR_FUSED_NORM_DW", "1") or 1)
+    # conv-FFN backward: norm2's dx arithmetic inside the depthwise-gradient kernel (ops.norm_dwconv_bwd_ok, where the fused forward above runs);
+    # a plain attribute: the A/B is parent commit against child commit (tools/rejected/README.md), tests switch it off for the two-node route
+    fused_convffn_bwd = True
     loose_grad_arena = os.environ.get("VPTR_GRAD_ARENA", "1") != "0"   # models without a trainer: `.grad` tensors are views of one buffer per model
     deterministic = False   # ops.set_deterministic / VPTR_DETERMINISTIC=1
 
