@@ -19,6 +19,15 @@ train_AutoEncoder.py:44-78; both NAR and FAR trainers take the optional adversar
 Every trainer also has the `train_flag=False` branch of its `single_iter` as `eval_step` (eval mode, no_grad, nothing a step owns is
 written; `capture_eval` makes it a hipGraph of its own), `step` / `eval_step` feed a `meters.DeviceLossMeters` without a host read, and
 `run_epoch` is the reference's loop over a loader (train_NAR.py:231-247).
+
+How the two stage-2 trainers are put together (`FARTrainer` subclasses `NARTrainer`):
+  * the iteration is sequenced once, `_forward(past, future, train)`: encoder, [train: zero the gradients, BatchNorm-buffer broadcast,]
+    transformer, decoder, discriminator terms (`_disc_update` / `_eval_disc`), recipe loss terms, generator's adversarial term.  A recipe
+    contributes `_encode` (what is encoded and fed to the transformer) and `_loss_terms`; `_step_impl` adds backward + exchange + optimizer
+    (`_finish`), `_eval_forward` is the same pass under `_eval_impl`'s eval mode;
+  * `capture`, `capture_front` and `capture_eval` are ONE procedure, `_capture` (warm-up on a side stream, pinned staging for the table
+    uploads, capture, node census, instantiate), parameterised by the warm-up pass, the captured body, whether the weight-gradient tuning is
+    waited for and settled, and whether a process group's watchdog thread runs beside the capture; `_replay` is the one replay prologue.
 """
 import os
 import time
@@ -330,14 +339,27 @@ class NARTrainer:
         `capture`, `capture_front`, `verify_graph` work as before: `trainer.opt.set_lr(...)` between replays changes the next update.  A
         skipped step leaves parameters, moments and step count untouched; it still refreshes the weight planes (from unchanged weights),
         still advances the dropout seed, and BatchNorm running statistics of the forward pass it belongs to have been updated already."""
+        self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
+                          schedule, skip_nonfinite)
+        # loss_name_list MSE / GDL(alpha=1) / BiPatchNCE(N, Tf, 8, 8, temperature 1.0) of train_NAR.py:176-179 run as the fused kernels of
+        # csrc/losses.hip (ops.mse_gdl, ops.nce_loss): plain kernel launches only, so the step can live in a hipGraph (DESIGN.md section 6)
+        self.nce_temperature = 1.0
+        self.lam_pc = lam_pc
+        if self.world > 1:
+            from .parallel import BufferSync
+            self._bufsync = BufferSync(self.T, 0, process_group)   # DDP's per-forward broadcast of rank 0's BatchNorm statistics
+
+    def _init_stage2(self, enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
+                     schedule, skip_nonfinite):
+        """what both stage-2 recipes construct: frozen auto-encoder, optional adversarial branch, the transformer's flat-slab optimizer"""
         self.enc, self.dec, self.T = enc.eval(), dec.eval(), transformer
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.bucket_elems = bucket_mb * (1 << 20) // 4
         self._init_gan(disc, lam_gan, lr, gan_mode, schedule, skip_nonfinite)
         # Stage 2 optimises the transformer only (train_NAR.py:205).  The reference nevertheless leaves the decoder's
-        # parameters trainable (:190-191), so its backward computes decoder weight gradients nobody consumes; that work
-        # is reproduced by default (dec_weight_grads=True) so that the measured step does everything the reference's does.
+        # parameters trainable (train_NAR.py:190-191, train_FAR.py:181-182), so its backward computes decoder weight gradients nobody
+        # consumes; that work is reproduced by default (dec_weight_grads=True) so that the measured step does everything the reference's does.
         for p in enc.parameters():
             p.requires_grad_(False)  # the encoder runs under no_grad (:54-56)
         for p in dec.parameters():
@@ -347,18 +369,7 @@ class NARTrainer:
             mod._vptr_frozen = True  # never stepped here: packed conv weights / eval-BN folds are cached (ops.frozen_weights)
         self.opt = FlatAdamW(self.T.parameters(), lr=lr, max_grad_norm=max_grad_norm, channel_last=_channel_last_ids(self.T),
                              schedule=schedule, skip_nonfinite=skip_nonfinite)
-        dev = self.opt.flat.device
-        # loss_name_list MSE / GDL(alpha=1) / BiPatchNCE(N, Tf, 8, 8, temperature 1.0) of train_NAR.py:176-179 run as the fused kernels of
-        # csrc/losses.hip (ops.mse_gdl, ops.nce_loss): plain kernel launches only, so the step can live in a hipGraph
-        self.nce_temperature = 1.0
-        self.lam_pc = lam_pc
         self._bufsync = None
-        if process_group is not None and torch.distributed.get_world_size(process_group) > 1:
-            from .parallel import BufferSync
-            self._bufsync = BufferSync(self.T, 0, process_group)   # DDP's per-forward broadcast of rank 0's BatchNorm statistics
-        self.pg = process_group
-        self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
-        self.bucket_elems = bucket_mb * (1 << 20) // 4
         self._graph = None
 
     _front = None          # data-parallel front graph (capture_front)
@@ -427,8 +438,19 @@ class NARTrainer:
         st["calls"] = st.get("calls", 0) + int(calls)
         st["steps"] = st.get("steps", 0) + 1
 
+    def _exchanges(self):
+        """whether the step's gradients cross the process group.  VPTR_DP_FORCE_EXCHANGE=1: take the exchange path on a one-rank group
+        too (a one-GPU box can then drive c10d's RCCL backend -- its own stream, async Work objects, event ordering against the
+        weight-gradient launches -- through the same code the 8-GPU job runs: tests/test_22_rccl_gpu.py, bench.py --force-exchange)"""
+        return self.pg is not None and (self.world > 1 or os.environ.get("VPTR_DP_FORCE_EXCHANGE") == "1")
+
+    @staticmethod
+    def _overlaps():
+        """whether the all-reduces are issued between the weight-gradient chunks (VPTR_DP_OVERLAP=0: one plain exchange after them)"""
+        return os.environ.get("VPTR_DP_OVERLAP", "1") != "0"
+
     def _allreduce_grads(self):
-        if self.pg is None or (self.world == 1 and os.environ.get("VPTR_DP_FORCE_EXCHANGE") != "1"):
+        if not self._exchanges():
             return
         from .parallel import allreduce_sum_
         tok = self._comm_begin()
@@ -441,12 +463,8 @@ class NARTrainer:
         rank the weight gradients are flushed in DP_CHUNKS grouped launches ordered by slab address; as soon as a chunk has
         been enqueued, the slab range below the next chunk's first destination is final and its all-reduce is issued
         asynchronously (RCCL runs it on its own stream), overlapping the next chunk's GEMM."""
-        # VPTR_DP_FORCE_EXCHANGE=1: take the exchange path on a one-rank group too (a one-GPU box can then drive c10d's RCCL backend
-        # -- its own stream, async Work objects, event ordering against the weight-gradient launches -- through the same code the
-        # 8-GPU job runs: tests/test_22_rccl_gpu.py, bench.py --force-exchange)
-        force = self.pg is not None and os.environ.get("VPTR_DP_FORCE_EXCHANGE") == "1"
         self._grad_scale = 1.0
-        if self.pg is None or (self.world == 1 and not force) or os.environ.get("VPTR_DP_OVERLAP", "1") == "0":
+        if not (self._exchanges() and self._overlaps()):
             loss.backward()
             ops.flush_wgrads()  # no-op: the grouped weight-gradient launch already ran at the end of backward
             self._allreduce_grads()
@@ -510,34 +528,47 @@ class NARTrainer:
         l_pc = ops.nce_loss(b.reshape(-1, C), a.reshape(-1, C), N * T, h * w, self.nce_temperature)
         return l_gdl + l_mse + self.lam_pc * l_pc, l_gdl, l_mse, l_pc
 
-    def _step_impl(self, past, future, front=False):
+    # -- the stage-2 iteration, sequenced once for train and eval; a recipe contributes `_encode` and `_loss_terms` ----------------------
+    def _encode(self, past, future):
+        """-> (what the transformer is fed, what `_loss_terms` needs of the encoder besides)"""
+        # train_NAR.py:54-56 encodes past and future in two calls; the encoder is per-frame (eval-mode BN), so one call on
+        # the concatenated clip gives the same features with twice the rows per conv GEMM (480 instead of 240 tiles)
+        if past.shape[0] == future.shape[0] and past.shape[2:] == future.shape[2:]:
+            feats = self.enc(torch.cat([past, future], dim=1))
+            return feats[:, :past.shape[1]], feats[:, past.shape[1]:]
+        return self.enc(past), self.enc(future)
+
+    def _loss_terms(self, pred_frames, pred_feats, past, future, future_feats):
+        """-> (the recipe's part of the loss, its terms by name)"""
+        loss, l_gdl, l_mse, l_pc = self.losses(pred_frames, future, pred_feats, future_feats)
+        return loss, {"T_GDL": l_gdl, "T_MSE": l_mse, "T_bpc": l_pc}
+
+    def _forward(self, past, future, train, front=False):
+        """-> (loss, terms): encoder, transformer, decoder, discriminator terms, recipe loss terms, generator's adversarial term"""
         with torch.no_grad():
-            # train_NAR.py:54-56 encodes past and future in two calls; the encoder is per-frame (eval-mode BN), so one call on
-            # the concatenated clip gives the same features with twice the rows per conv GEMM (480 instead of 240 tiles)
-            if past.shape[0] == future.shape[0] and past.shape[2:] == future.shape[2:]:
-                feats = self.enc(torch.cat([past, future], dim=1))
-                past_feats, future_feats = feats[:, :past.shape[1]], feats[:, past.shape[1]:]
-            else:
-                past_feats, future_feats = self.enc(past), self.enc(future)
-        if not self.T.training:   # nn.Module.train() walks ~500 sub-modules: ~5 ms of host time per step
-            self.T.train()
-        self.opt.zero_grad()
-        if self.dec_weight_grads:
-            self.dec.zero_grad(set_to_none=True)  # train_NAR.py:61
-        if self._bufsync and not front:      # a collective: the front-graph step issues it eagerly before the replay
-            self._bufsync.sync()
-        pred_feats = self.T(past_feats)
+            feats, aux = self._encode(past, future)
+        if train:
+            if not self.T.training:   # nn.Module.train() walks ~500 sub-modules: ~5 ms of host time per step
+                self.T.train()
+            self.opt.zero_grad()
+            if self.dec_weight_grads:
+                self.dec.zero_grad(set_to_none=True)  # train_NAR.py:61
+            if self._bufsync and not front:      # a collective: the front-graph step issues it eagerly before the replay
+                self._bufsync.sync()
+        pred_feats = self.T(feats)
         pred_frames = self.dec(pred_feats)
         extra = {}
-        if self.disc is not None:
-            extra = self._disc_update(pred_frames, future)
-        loss, l_gdl, l_mse, l_pc = self.losses(pred_frames, future, pred_feats, future_feats)
+        if self.disc is not None:                # cal_lossD(VPTR_Disc, pred_frames, future_frames): train_NAR.py:73,96, train_FAR.py:72,93
+            extra = self._disc_update(pred_frames, future) if train else self._eval_disc(pred_frames, future)
+        loss, terms = self._loss_terms(pred_frames, pred_feats, past, future, aux)
         if self.disc is not None:
             extra["T_gan"] = self.gan(self.disc(pred_frames.flatten(0, 1)), True)
             loss = loss + self.lam_gan * extra["T_gan"]
-            extra["T_gan"] = extra["T_gan"].detach()
-        return self._finish(loss, dict({"T_total": loss.detach(), "T_GDL": l_gdl.detach(), "T_MSE": l_mse.detach(), "T_bpc": l_pc.detach()},
-                                       **extra), front)
+        return loss, dict({"T_total": loss}, **terms, **extra)
+
+    def _step_impl(self, past, future, front=False):
+        loss, terms = self._forward(past, future, True, front)
+        return self._finish(loss, {k: v.detach() for k, v in terms.items()}, front)
 
     def step(self, past, future, meters=None):
         """one train step (a replay when `capture` / `capture_front` ran); meters: a `meters.DeviceLossMeters` that receives the returned
@@ -547,38 +578,38 @@ class NARTrainer:
             meters.update(out)
         return out
 
+    def _replay(self, g, static_past, static_future, past, future, bufsync=False):
+        """fill a captured graph's static inputs and replay it.  Replays are stream-ordered like any other launch;
+        tests/test_20_graph_gpu.py compares them with eager steps (the round-1 corruption was a captured table upload reading a
+        recycled pinned buffer: ops._to_device_async)"""
+        if self.opt.planes is not None and self.opt.planes.stale():
+            self.opt.planes.refresh()   # parameters were changed from outside (load_state_dict) since the last replay
+        _copy_into(static_past, past)
+        _copy_into(static_future, future)
+        if bufsync and self._bufsync:
+            self._bufsync.sync()
+        g.replay()
+
     def _step(self, past, future):
         if self._front is not None:
             # data-parallel step: forward + backward replayed as one hipGraph, then the part that talks to other ranks runs eagerly --
             # DP_CHUNKS grouped weight-gradient launches on the recorded operands (static addresses in the graph's pool), the all-reduces
             # between them, the optimizer (3 launches)
-            if self.opt.planes is not None and self.opt.planes.stale():
-                self.opt.planes.refresh()
-            _copy_into(self._static_past, past)
-            _copy_into(self._static_future, future)
-            if self._bufsync:
-                self._bufsync.sync()
-            self._front.replay()
+            self._replay(self._front, self._static_past, self._static_future, past, future, bufsync=True)
             ops.requeue_wgrads(self._front_items)
             self._grad_scale = 1.0
-            if os.environ.get("VPTR_DP_OVERLAP", "1") == "0":
+            if self._overlaps():
+                self._exchange_held_wgrads()
+            else:
                 ops.flush_wgrads()
                 self._allreduce_grads()
-            else:
-                self._exchange_held_wgrads()
             self.opt.step(grad_scale=self._grad_scale)
             self._static_out["grad_norm"] = self.opt.grad_norm()
             if self.opt.ctl is not None:
                 self._static_out["lr"], self._static_out["skipped"] = self.opt.lr_now(), self.opt.skipped()
             return self._static_out
         if self._graph is not None:
-            # replays are stream-ordered like any other launch; tests/test_20_graph_gpu.py compares them with eager steps (the
-            # round-1 corruption was a captured table upload reading a recycled pinned buffer: ops._to_device_async)
-            if self.opt.planes is not None and self.opt.planes.stale():
-                self.opt.planes.refresh()   # parameters were changed from outside (load_state_dict) since the last replay
-            _copy_into(self._static_past, past)
-            _copy_into(self._static_future, future)
-            self._graph.replay()
+            self._replay(self._graph, self._static_past, self._static_future, past, future)
             return self._static_out
         return self._step_impl(past, future)
 
@@ -591,55 +622,75 @@ class NARTrainer:
                 if getattr(m, a, None) is not None]
 
     @staticmethod
-    def _warm_up_for_capture(warmup, step, any_rank=None):
+    def _warm_up_for_capture(warmup, step, any_rank=None, tune=True):
         """eager steps in front of a capture: `warmup` - 1 of them, then as many more as the tile-row tuning of the grouped weight-gradient
         launches still wants (ops.wgrad_tune_open: each setting is timed ops._TUNE_SAMPLES times, the first, cold sample not counted), then
         the geometry is FIXED (ops.wgrad_tune_settle) and one last step issues exactly the launches -- and table uploads, counted in
         ops._upload_stats -- the capture will issue.  Whether a timing has been booked depends on how far this host runs ahead of its
         GPU, so with several ranks (`any_rank`: True if the flag holds on any rank) every rank takes the same number of extra steps: each
-        of them issues the step's all-reduces, and a rank that stopped early would pair its next collective with another rank's step."""
+        of them issues the step's all-reduces, and a rank that stopped early would pair its next collective with another rank's step.
+        tune=False (a validation pass, which launches no weight gradients): the tuning is neither waited for nor settled -- settling
+        would fix the geometry for a later train capture."""
         for _ in range(max(warmup, 1) - 1):
             step()
-        extra = 0
-        while extra < 2 * ops._TUNE_SAMPLES and (any_rank(ops.wgrad_tune_open()) if any_rank else ops.wgrad_tune_open()):
-            step()
-            extra += 1
-        ops.wgrad_tune_settle()
+        if tune:
+            extra = 0
+            while extra < 2 * ops._TUNE_SAMPLES and (any_rank(ops.wgrad_tune_open()) if any_rank else ops.wgrad_tune_open()):
+                step()
+                extra += 1
+            ops.wgrad_tune_settle()
         ops._upload_stats.update(count=0, max_bytes=0)
         step()
+
+    def _capture(self, past, future, warmup, eager, body, what, census, tune=True, any_rank=None, beside_collectives=False):
+        """The capture procedure of `capture`, `capture_front` and `capture_eval` -> (graph, what `body` returned, static past, static
+        future, scratch to keep alive).  `past`/`future` give the static shapes; `eager(past, future)` is one warm-up pass on a side
+        stream, `body(past, future)` what is captured; `census` names the attribute that receives the node census and `what` the
+        captured thing in the error text; `tune`, `any_rank`: see `_warm_up_for_capture`.
+
+        The captured graph is inspected before it is instantiated: it must consist of kernel, memcpy and empty nodes only.  A MEMSET
+        node (hipMemsetAsync under capture -- ATen's multi-block reductions zero their semaphores that way) writes garbage from
+        the second replay on with this HIP runtime (tools/memset_node_probe.py), which is what corrupted the round-2 graph
+        (F.normalize's backward in the BiPatchNCE branch); the step's own losses are plain kernels now (csrc/losses.hip) and
+        any memset node that sneaks back in raises here instead of silently training on garbage."""
+        past, future = past.clone(), future.clone()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._warm_up_for_capture(warmup, lambda: eager(past, future), any_rank, tune)
+        torch.cuda.current_stream().wait_stream(s)
+        # the captured pass uploads as many host-built tables as the last warm-up pass did (grouped launches: 2 per group, more with
+        # the GAN branch or non-P16 groups); each gets a pinned buffer of its own that lives as long as the graph
+        ops.reserve_graph_staging(count=ops._upload_stats["count"] + 4, nbytes=max(1 << 16, 2 * ops._upload_stats["max_bytes"]))
+        if tune:
+            ops.wgrad_tune_settle()
+        if beside_collectives:
+            # c10d's RCCL watchdog thread polls the events of earlier collectives (hipEventQuery): under the default GLOBAL capture mode
+            # that call, made while THIS thread captures, aborts the process ("operation not permitted when stream is capturing").  Drain
+            # the device first (no work left to poll) and capture in thread-local mode (other threads' calls stay legal).
+            torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph(keep_graph=True)
+        with torch.cuda.graph(g, capture_error_mode="thread_local" if beside_collectives else "global"):
+            out = body(past, future)
+        nodes = graph_node_census(g)
+        setattr(self, census, nodes)
+        bad = {k: v for k, v in nodes.items() if k not in ("kernel", "memcpy", "empty")}
+        if bad:
+            g.reset()
+            raise RuntimeError("captured %s holds node types that are not replay-safe on this HIP runtime: %s (all nodes: %s)" % (what, bad, nodes))
+        g.instantiate()
+        return g, out, past, future, self._module_scratch()
 
     def capture(self, past, future, warmup=3):
         """Capture the whole step (forward, losses, backward, clip, AdamW) into one hipGraph.  `past`/`future` give the
         static shapes; real data is copied into the captured input buffers by `step`.
 
-        The captured graph is inspected before it is instantiated: it must consist of kernel and memcpy nodes only.  A MEMSET
-        node (hipMemsetAsync under capture -- ATen's multi-block reductions zero their semaphores that way) writes garbage from
-        the second replay on with this HIP runtime (tools/memset_node_probe.py), which is what corrupted the round-2 graph
-        (F.normalize's backward in the BiPatchNCE branch); the step's own losses are plain kernels now (csrc/losses.hip) and
-        any memset node that sneaks back in raises here instead of silently training on garbage."""
+        The procedure, and the node census it refuses a graph on, is `_capture`'s."""
         if self.pg is not None and self.world > 1:
             raise RuntimeError("graph capture of the data-parallel step is not enabled (RCCL calls stay eager)")
-        self._static_past, self._static_future = past.clone(), future.clone()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._warm_up_for_capture(warmup, lambda: self._step_impl(self._static_past, self._static_future))
-        torch.cuda.current_stream().wait_stream(s)
-        # the captured step uploads as many host-built tables as the last warm-up step did (grouped launches: 2 per group, more with
-        # the GAN branch or non-P16 groups); each gets a pinned buffer of its own that lives as long as the graph
-        ops.reserve_graph_staging(count=ops._upload_stats["count"] + 4, nbytes=max(1 << 16, 2 * ops._upload_stats["max_bytes"]))
-        ops.wgrad_tune_settle()
-        g = torch.cuda.CUDAGraph(keep_graph=True)
-        with torch.cuda.graph(g):
-            self._static_out = self._step_impl(self._static_past, self._static_future)
-        self.graph_nodes = graph_node_census(g)
-        bad = {k: v for k, v in self.graph_nodes.items() if k not in ("kernel", "memcpy", "empty")}
-        if bad:
-            g.reset()
-            raise RuntimeError("captured step holds node types that are not replay-safe on this HIP runtime: %s (all nodes: %s)"
-                               % (bad, self.graph_nodes))
-        g.instantiate()
-        self._graph, self._graph_scratch = g, self._module_scratch()
+        g, self._static_out, self._static_past, self._static_future, self._graph_scratch = self._capture(
+            past, future, warmup, self._step_impl, self._step_impl, "step", "graph_nodes")
+        self._graph = g
         return g
 
     def capture_front(self, past, future, warmup=3):
@@ -652,30 +703,10 @@ class NARTrainer:
             raise RuntimeError("capture_front: the adversarial branch all-reduces inside the step; run it eagerly")
         if self.pg is None:
             raise RuntimeError("capture_front is the data-parallel capture; use capture() without a process group")
-        self._static_past, self._static_future = past.clone(), future.clone()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._warm_up_for_capture(warmup, lambda: self._step_impl(self._static_past, self._static_future), self._any_rank)
-        torch.cuda.current_stream().wait_stream(s)
-        ops.reserve_graph_staging(count=ops._upload_stats["count"] + 4, nbytes=max(1 << 16, 2 * ops._upload_stats["max_bytes"]))
-        ops.wgrad_tune_settle()
-        # c10d's RCCL watchdog thread polls the events of earlier collectives (hipEventQuery): under the default GLOBAL capture mode
-        # that call, made while THIS thread captures, aborts the process ("operation not permitted when stream is capturing").  Drain
-        # the device first (no work left to poll) and capture in thread-local mode (other threads' calls stay legal).
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph(keep_graph=True)
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._static_out = self._front_impl(self._static_past, self._static_future)
-            self._front_items = ops.take_wgrads()
-        self.graph_nodes = graph_node_census(g)
-        bad = {k: v for k, v in self.graph_nodes.items() if k not in ("kernel", "memcpy", "empty")}
-        if bad:
-            g.reset()
-            raise RuntimeError("captured step holds node types that are not replay-safe on this HIP runtime: %s (all nodes: %s)"
-                               % (bad, self.graph_nodes))
-        g.instantiate()
-        self._front, self._graph_scratch = g, self._module_scratch()
+        g, (self._static_out, self._front_items), self._static_past, self._static_future, self._graph_scratch = self._capture(
+            past, future, warmup, self._step_impl, lambda p, f: (self._front_impl(p, f), ops.take_wgrads()),
+            "step", "graph_nodes", any_rank=self._any_rank, beside_collectives=True)
+        self._front = g
         return g
 
     def _any_rank(self, flag):
@@ -715,19 +746,7 @@ class NARTrainer:
         return {"Dtotal": (l_fake + l_real) * 0.5 * self.lam_gan, "Dfake": l_fake, "Dreal": l_real}
 
     def _eval_forward(self, past, future):
-        if past.shape[0] == future.shape[0] and past.shape[2:] == future.shape[2:]:   # the concatenated call of _step_impl
-            feats = self.enc(torch.cat([past, future], dim=1))
-            past_feats, future_feats = feats[:, :past.shape[1]], feats[:, past.shape[1]:]
-        else:
-            past_feats, future_feats = self.enc(past), self.enc(future)
-        pred_feats = self.T(past_feats)
-        pred_frames = self.dec(pred_feats)
-        extra = self._eval_disc(pred_frames, future) if self.disc is not None else {}
-        loss, l_gdl, l_mse, l_pc = self.losses(pred_frames, future, pred_feats, future_feats)
-        if self.disc is not None:
-            extra["T_gan"] = self.gan(self.disc(pred_frames.flatten(0, 1)), True)
-            loss = loss + self.lam_gan * extra["T_gan"]
-        return dict({"T_total": loss, "T_GDL": l_gdl, "T_MSE": l_mse, "T_bpc": l_pc}, **extra)
+        return self._forward(past, future, False)[1]
 
     @torch.no_grad()
     def _eval_impl(self, past, future):
@@ -756,11 +775,7 @@ class NARTrainer:
         mode.  meters: as in `step`."""
         g = self._eval_graph
         if g is not None and past.shape == self._eval_past.shape and future.shape == self._eval_future.shape:
-            if self.opt.planes is not None and self.opt.planes.stale():
-                self.opt.planes.refresh()
-            _copy_into(self._eval_past, past)
-            _copy_into(self._eval_future, future)
-            g.replay()
+            self._replay(g, self._eval_past, self._eval_future, past, future)
             out = self._eval_out
         else:
             out = self._eval_impl(past, future)
@@ -769,76 +784,59 @@ class NARTrainer:
         return out
 
     def capture_eval(self, past, future, warmup=2):
-        """`capture` for the validation pass: eager warm-ups on a side stream, pinned staging reserved for the table uploads of one pass,
-        a single-stream capture, the node census (kernel / memcpy / empty nodes only).  The eval graph has static inputs and outputs of
-        its own, so it coexists with a train graph; it holds no collective, so it is allowed under a multi-rank group."""
-        self._eval_past, self._eval_future = past.clone(), future.clone()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(max(warmup, 1) - 1):
-                self._eval_impl(self._eval_past, self._eval_future)
-            ops._upload_stats.update(count=0, max_bytes=0)
-            self._eval_impl(self._eval_past, self._eval_future)
-        torch.cuda.current_stream().wait_stream(s)
-        ops.reserve_graph_staging(count=ops._upload_stats["count"] + 4, nbytes=max(1 << 16, 2 * ops._upload_stats["max_bytes"]))
-        g = torch.cuda.CUDAGraph(keep_graph=True)
-        with torch.cuda.graph(g):
-            out = self._eval_impl(self._eval_past, self._eval_future)
-        self.eval_graph_nodes = graph_node_census(g)
-        bad = {k: v for k, v in self.eval_graph_nodes.items() if k not in ("kernel", "memcpy", "empty")}
-        if bad:
-            g.reset()
-            raise RuntimeError("captured validation pass holds node types that are not replay-safe on this HIP runtime: %s (all nodes: %s)"
-                               % (bad, self.eval_graph_nodes))
-        g.instantiate()
-        self._eval_out, self._eval_graph, self._eval_scratch = out, g, self._module_scratch()
+        """`capture` for the validation pass (the same procedure, `_capture`).  An eval pass launches no weight gradients, so their
+        tile-row tuning is neither waited for nor settled.  The eval graph has static inputs and outputs of its own, so it coexists with
+        a train graph; it holds no collective, so it is allowed under a multi-rank group."""
+        g, self._eval_out, self._eval_past, self._eval_future, self._eval_scratch = self._capture(
+            past, future, warmup, self._eval_impl, self._eval_impl, "validation pass", "eval_graph_nodes", tune=False)
+        self._eval_graph = g
         return g
+
+    def has_graph(self, train=True):
+        """whether `step` (train) / `eval_step` replays a captured graph"""
+        return (self._graph is not None or self._front is not None) if train else self._eval_graph is not None
 
     def static_inputs(self, train=True):
         """the (past, future) buffers the train (`capture` / `capture_front`) or eval (`capture_eval`) graph reads.  `step` / `eval_step`
         skip their copy when handed exactly these tensors: write a batch there once -- `ClipIngest(...)(raw, out=trainer.static_inputs())`"""
-        if train:
-            if self._graph is None and self._front is None:
-                raise RuntimeError("static_inputs: capture() / capture_front() first")
-            return self._static_past, self._static_future
-        if self._eval_graph is None:
-            raise RuntimeError("static_inputs(train=False): capture_eval() first")
-        return self._eval_past, self._eval_future
+        if not self.has_graph(train):
+            raise RuntimeError("static_inputs: capture() / capture_front() first" if train else "static_inputs(train=False): capture_eval() first")
+        return (self._static_past, self._static_future) if train else (self._eval_past, self._eval_future)
 
     # -- replay == eager, checked on the live model (bench.py runs this before it times a graph) -------------------------------------
+    @staticmethod
+    def _slab_state(opt, module):
+        """copies of what a step writes of one optimizer and the module it steps: slabs, step count, controls record, module buffers"""
+        s = {"flat": opt.flat.clone(), "m": opt.m.clone(), "v": opt.v.clone(), "step": opt.step_dev.clone(),
+             "buffers": [b.detach().clone() for b in module.buffers()]}
+        if opt.ctl is not None:   # the controls' device-written record: last rate, skip counters, the update scalars
+            s["ctl"] = opt.ctl.state.clone()
+        return s
+
+    @staticmethod
+    def _load_slab_state(opt, module, s):
+        opt.flat.copy_(s["flat"]); opt.m.copy_(s["m"]); opt.v.copy_(s["v"]); opt.step_dev.copy_(s["step"])
+        for b, v in zip(module.buffers(), s["buffers"]):
+            b.copy_(v)
+        if "ctl" in s:
+            opt.ctl.state.copy_(s["ctl"])
+
     def _snapshot(self):
-        dev = self.opt.flat.device
-        snap = {"flat": self.opt.flat.clone(), "m": self.opt.m.clone(), "v": self.opt.v.clone(), "step": self.opt.step_dev.clone(),
-                "buffers": [b.detach().clone() for b in self.T.buffers()], "seed": ops._master_seed(dev).clone()}
-        if self.opt.ctl is not None:   # the controls' device-written record: last rate, skip counters, the update scalars
-            snap["ctl"] = self.opt.ctl.state.clone()
+        snap = self._slab_state(self.opt, self.T)
+        snap["seed"] = ops._master_seed(self.opt.flat.device).clone()
         if self.disc is not None:   # the adversarial branch steps a second slab and the discriminator's BatchNorm statistics
-            o = self.opt_D
-            snap["D"] = {"flat": o.flat.clone(), "m": o.m.clone(), "v": o.v.clone(), "step": o.step_dev.clone(),
-                         "buffers": [b.detach().clone() for b in self.disc.buffers()]}
-            if o.ctl is not None:
-                snap["D"]["ctl"] = o.ctl.state.clone()
+            snap["D"] = self._slab_state(self.opt_D, self.disc)
         return snap
 
     def _restore(self, snap):
         dev = self.opt.flat.device
         with torch.no_grad():
-            self.opt.flat.copy_(snap["flat"]); self.opt.m.copy_(snap["m"]); self.opt.v.copy_(snap["v"]); self.opt.step_dev.copy_(snap["step"])
-            for b, v in zip(self.T.buffers(), snap["buffers"]):
-                b.copy_(v)
+            self._load_slab_state(self.opt, self.T, snap)
             ops._master_seed(dev).copy_(snap["seed"])
-            if "ctl" in snap:
-                self.opt.ctl.state.copy_(snap["ctl"])
             if self.disc is not None:
-                o, d = self.opt_D, snap["D"]
-                o.flat.copy_(d["flat"]); o.m.copy_(d["m"]); o.v.copy_(d["v"]); o.step_dev.copy_(d["step"])
-                if "ctl" in d:
-                    o.ctl.state.copy_(d["ctl"])
-                for b, v in zip(self.disc.buffers(), d["buffers"]):
-                    b.copy_(v)
-                if o.planes is not None:
-                    o.planes.refresh()
+                self._load_slab_state(self.opt_D, self.disc, snap["D"])
+                if self.opt_D.planes is not None:
+                    self.opt_D.planes.refresh()
         ops._seed_scope.pop(ops._dev_key(dev), None)
         if self.opt.planes is not None:
             self.opt.planes.refresh()
@@ -860,7 +858,7 @@ class NARTrainer:
             round-2 corruption began at the second replay).
           * trajectory (`traj_rtol`, loose, plus finiteness): `steps` back-to-back replays with no host read in between vs `steps`
             eager steps from the same initial state."""
-        if self._graph is None and self._front is None:
+        if not self.has_graph():
             raise RuntimeError("verify_graph: capture() / capture_front() first")
         snap0 = self._snapshot()
         kind = "_graph" if self._graph is not None else "_front"
@@ -920,54 +918,17 @@ class FARTrainer(NARTrainer):
     def __init__(self, enc, dec, transformer, lr=1e-4, max_grad_norm=1.0, process_group=None, bucket_mb=64, dec_weight_grads=True,
                  disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False):
         """schedule / skip_nonfinite: as in `NARTrainer`"""
-        self.enc, self.dec, self.T = enc.eval(), dec.eval(), transformer
-        self.pg = process_group
-        self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
-        self.bucket_elems = bucket_mb * (1 << 20) // 4
-        self._init_gan(disc, lam_gan, lr, gan_mode, schedule, skip_nonfinite)
-        for p in enc.parameters():
-            p.requires_grad_(False)
-        for p in dec.parameters():
-            p.requires_grad_(bool(dec_weight_grads))  # train_FAR.py:181-182 leaves the decoder trainable (never stepped)
-        self.dec_weight_grads = bool(dec_weight_grads)
-        for mod in list(self.enc.modules()) + list(self.dec.modules()):
-            mod._vptr_frozen = True
-        self.opt = FlatAdamW(self.T.parameters(), lr=lr, max_grad_norm=max_grad_norm, channel_last=_channel_last_ids(self.T),
-                             schedule=schedule, skip_nonfinite=skip_nonfinite)
-        self._bufsync = None   # the FAR transformer has no BatchNorm (LayerNorm conv-FFNs): nothing to broadcast per forward
-        self._graph = None
+        # no BufferSync: the FAR transformer has no BatchNorm (LayerNorm conv-FFNs), nothing to broadcast per forward
+        self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
+                          schedule, skip_nonfinite)
 
-    def _step_impl(self, past, future, front=False):
-        with torch.no_grad():
-            gt_feats = self.enc(torch.cat([past, future[:, :-1]], dim=1))    # train_FAR.py:53-55
-        if not self.T.training:   # nn.Module.train() walks ~500 sub-modules: ~5 ms of host time per step
-            self.T.train()
-        self.opt.zero_grad()
-        if self.dec_weight_grads:
-            self.dec.zero_grad(set_to_none=True)
-        pred_frames = self.dec(self.T(gt_feats))
-        extra = {}
-        if self.disc is not None:                                            # cal_lossD(VPTR_Disc, pred_frames, future_frames) :72
-            extra = self._disc_update(pred_frames, future)
+    def _encode(self, past, future):
+        return self.enc(torch.cat([past, future[:, :-1]], dim=1)), None    # train_FAR.py:53-55
+
+    def _loss_terms(self, pred_frames, pred_feats, past, future, aux):
         real = torch.cat([past[:, 1:], future], dim=1)                       # :80
         l_mse, l_gdl = ops.mse_gdl(pred_frames, real)                        # cal_lossT :32-46
-        loss = l_gdl + l_mse
-        if self.disc is not None:
-            t_gan = self.gan(self.disc(pred_frames.flatten(0, 1)), True)
-            loss = loss + self.lam_gan * t_gan
-            extra["T_gan"] = t_gan.detach()
-        return self._finish(loss, dict({"T_total": loss.detach(), "T_GDL": l_gdl.detach(), "T_MSE": l_mse.detach()}, **extra), front)
-
-    def _eval_forward(self, past, future):
-        gt_feats = self.enc(torch.cat([past, future[:, :-1]], dim=1))        # train_FAR.py:53-55
-        pred_frames = self.dec(self.T(gt_feats))
-        extra = self._eval_disc(pred_frames, future) if self.disc is not None else {}   # cal_lossD(pred_frames, future_frames) :93
-        l_mse, l_gdl = ops.mse_gdl(pred_frames, torch.cat([past[:, 1:], future], dim=1))
-        loss = l_gdl + l_mse
-        if self.disc is not None:
-            extra["T_gan"] = self.gan(self.disc(pred_frames.flatten(0, 1)), True)
-            loss = loss + self.lam_gan * extra["T_gan"]
-        return dict({"T_total": loss, "T_GDL": l_gdl, "T_MSE": l_mse}, **extra)
+        return l_gdl + l_mse, {"T_GDL": l_gdl, "T_MSE": l_mse}
 
     @torch.no_grad()
     def predict(self, past, num_pred, kv_cache=False):
@@ -999,6 +960,10 @@ class AETrainer:
         self.opt_D = FlatAdamW(list(disc.parameters()), lr=lr, betas=betas, weight_decay=0.0, schedule=schedule, skip_nonfinite=skip_nonfinite)
         self.gan = GANLoss(gan_mode, target_real_label=1.0, target_fake_label=0.0).to(self.opt_G.flat.device)
         self.lam_gan = lam_gan
+
+    def has_graph(self, train=True):
+        """the stage-1 step is not captured"""
+        return False
 
     def step(self, past, future, meters=None):
         out = self._step(past, future)
@@ -1068,8 +1033,7 @@ def run_epoch(trainer, loader, train, meters, ingest=None):
     inputs when the trainer has captured one for this mode and the batch fits it."""
     fn = trainer.step if train else trainer.eval_step
     static = None
-    if ingest is not None and (getattr(trainer, "_eval_graph", None) if not train
-                               else getattr(trainer, "_graph", None) or getattr(trainer, "_front", None)) is not None:
+    if ingest is not None and trainer.has_graph(train):
         static = trainer.static_inputs(train=train)
     for sample in loader:
         if ingest is None:
