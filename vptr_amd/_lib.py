@@ -151,6 +151,13 @@ CONVFFN_SIGNATURES = {
     "vptr_norm_act_bwd_sums": [P, P, P, P, P, P, P, P, P, I, I, I, I, F, P, U, P, P],
     "vptr_dwconv3x3_norm_bwd": [P, P, P, P, P, P, P, I, F, P, U, P, P, P, P, P, I, I, I, I, I, P],
 }
+# gradient accumulation and EMA weights of the optimizer controls, declared in include/vptr_hip_accum.h (additive as well)
+ACCUM_SIGNATURES = {
+    "vptr_accum_begin": [P, L, P, P],
+    "vptr_optim_prepare_accum": [P, P, P, P, P, P],
+    "vptr_adamw_ctl_ema": [P, P, P, P, P, L, P, P, P],
+    "vptr_slab_swap": [P, P, L, P],
+}
 
 
 def _load():
@@ -159,7 +166,7 @@ def _load():
             "vptr_amd: %s is missing. Build it with `python -m vptr_amd.build` (needs hipcc, gfx950). "
             "There is no CPU / PyTorch fallback for the VPTR hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()):
+    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.argtypes = argt
         fn.restype = c_int

@@ -107,7 +107,7 @@ class DeviceLossMeters:
     step with optimizer controls adds, 'lr' / 'skipped' ...; any of them is metered when it is listed in `names`).
     add: backend `add(terms, state, weight)` with `terms` the K tensors in row order (None = absent); default: the HIP kernel."""
 
-    def __init__(self, names, device, ignore=("grad_norm", "lr", "skipped", "lr_G", "lr_D", "skipped_G", "skipped_D"), add=None):
+    def __init__(self, names, device, ignore=("grad_norm", "lr", "skipped", "lr_G", "lr_D", "skipped_G", "skipped_D", "applied"), add=None):
         self.names = list(names)
         if not 1 <= len(self.names) <= MAX_TERMS or len(set(self.names)) != len(self.names):
             raise ValueError("DeviceLossMeters: 1 .. %d distinct names, got %r" % (MAX_TERMS, self.names))

@@ -64,11 +64,57 @@ def defer_partial_reduce(part, dst0, dst1, nparts, C):
         pass
 
 
+def _accumulating_ranges():
+    """address ranges of the registered gradient slabs that hold partial sums across backward passes (FlatAdamW with accum_steps= /
+    ema_decay= marks its slab `_vptr_accumulates`); empty for every other trainer, whose launches then stay exactly as they were"""
+    from .grads import _flat_slabs
+    out = []
+    for _, _, _, gref in _flat_slabs:
+        g = gref()
+        if g is not None and getattr(g, "_vptr_accumulates", False):
+            out.append((g.data_ptr(), g.data_ptr() + g.numel() * 4))
+    return out
+
+
+def _split_repeats(items, key):
+    """deterministic mode, destinations inside an accumulating slab only -> (later occurrences of a destination as rounds, the rest)"""
+    ranges = _accumulating_ranges() if config.deterministic else []
+    if not ranges:
+        return [], items
+    inside = lambda it: any(lo <= key(it)[0] < hi for lo, hi in ranges)
+    rounds = _by_occurrence([it for it in items if inside(it)], key)
+    first = set(id(it) for it in rounds[0]) if rounds else set()
+    return rounds[1:], [it for it in items if not inside(it) or id(it) in first]
+
+
+def _by_occurrence(items, key):
+    """items split into rounds: round r holds the (r + 1)-th record of every key, in recording order (no key twice in a round)"""
+    seen, rounds = {}, []
+    for it in items:
+        k = key(it)
+        r = seen.get(k, 0)
+        seen[k] = r + 1
+        if r == len(rounds):
+            rounds.append([])
+        rounds[r].append(it)
+    return rounds
+
+
 def flush_partial_reduces():
     if not _reduce_q:
         return
     items = list(_reduce_q)
     del _reduce_q[:]
+    # two records with one destination would meet in atomics (`unique` below): order-dependent as soon as the destination is not zero
+    # (an open accumulation window).  Deterministic mode on an accumulating slab: one launch sequence per occurrence instead, later
+    # occurrences first, as flush_wgrads does
+    later, items = _split_repeats(items, lambda it: (it[1].data_ptr(), it[2].data_ptr() if it[2] is not None else 0))
+    for part in later:
+        _launch_partial_reduces(part)
+    _launch_partial_reduces(items)
+
+
+def _launch_partial_reduces(items):
     # one table, one upload; entries sorted by width and launched per width class (the grid is sized for the widest entry of a launch:
     # the 528-wide LayerNorm rows must not ride on the grid of the 135 168-wide LayerNorm((F,H,W)) rows)
     items.sort(key=lambda it: it[4])
@@ -434,6 +480,14 @@ def flush_wgrads(chunks=1, on_chunk=None):
         return
     items = list(_wgrad_q)
     del _wgrad_q[:]
+    # A module applied twice in one forward (the NAR model's NCE projector) records two problems with ONE destination.  In one launch
+    # their tiles meet in fp32 atomics: from a zero-filled slab a + b is order-independent, into the partial sum c of an open
+    # accumulation window (c + a) + b is not.  Deterministic mode on an accumulating slab (`_split_repeats`; no other trainer's launches
+    # change): the second and later occurrences, in the order the backward pass recorded them, get launches of their own ahead of the
+    # rest: every destination then has one adder per launch, and the stream orders the launches
+    later_rounds, items = _split_repeats(items, lambda it: (it[2].data_ptr(),))
+    for later in later_rounds:
+        _launch_wgrad_group(sorted(later, key=lambda it: (-it[3] * it[4], it[2].data_ptr())), allow_sync=chunks <= 1)
     if chunks <= 1 or len(items) < 2 * chunks:
         # largest problems first (their 51-tile waves fill the chip; the 15-tile problems then pack the tail), problems that read the
         # same X next to each other: 8.55 -> 8.42 ms on the K64 step's 196 problems (round-4 A/B)

@@ -23,6 +23,10 @@ H_BASE_LR, H_BETA1, H_BETA2, H_EPS, H_WEIGHT_DECAY, H_MAX_NORM, H_GRAD_SCALE, H_
 H_SCHED_KIND, H_WARMUP_STEPS, H_TOTAL_STEPS, H_MIN_RATIO = range(8, 12)
 S_LR_NOW, S_GRAD_NORM, S_SKIP_NOW, S_SKIPPED_TOTAL, S_SKIPPED_IN_A_ROW, S_COEF, S_STEP_SIZE, S_INV_SQRT_BC2, S_DECAY, S_OB1, S_OB2 = range(11)
 S_BETA1, S_BETA2, S_EPS = 11, 12, 13
+# word indices of the third record, `window` (include/vptr_hip_accum.h): words 0 .. 7 are the host's, 8 .. 15 the device's
+W_ACCUM_STEPS, W_EMA_DECAY, W_EMA_WARMUP = range(3)
+W_MICRO, W_APPLY_NOW, W_EMA_OMD, W_EMA_UPDATES = range(8, 12)
+SKIP_HOLD = 2.0            # state[S_SKIP_NOW] while a window is open (0 apply, 1 skipped)
 WORDS = 16
 MAX_STEPS = 1 << 24        # W and S travel as fp32 words, and the step counter is an fp32 too: whole numbers are exact below 2^24
 
@@ -104,21 +108,37 @@ def _finite(name, x, lo=None, lo_open=False, hi=None, hi_open=False):
 
 
 class OptimControls:
-    """The two device records of one optimizer and the launches on them.  `hyper` is written by the host only, one fill kernel per changed
+    """The device records of one optimizer and the launches on them.  `hyper` is written by the host only, one fill kernel per changed
     word (stream-ordered, no memset node, no host buffer whose lifetime a graph would have to care about); `state` is written by the device
-    only, apart from the zeroing here and `load_counters`."""
+    only, apart from the zeroing here and `load_counters`.
 
-    def __init__(self, device, lr, betas, eps, weight_decay, max_grad_norm, schedule=None, skip_nonfinite=False):
+    accum_steps / ema_decay (either one not None) add the third record, `window` (include/vptr_hip_accum.h): gradient accumulation over
+    `accum_steps` micro-steps and the EMA of the parameters.  Its words 0 .. 7 are the host's (the same one-fill-per-changed-word writes),
+    words 8 .. 15 the device's, apart from the zeroing here, `reset_window` and `load_window`.  `micro_host` mirrors the window position:
+    it is deterministic, because neither a hold nor a skipped close moves a window boundary."""
+
+    window = None      # the third record; None: no accumulation window, `prepare` / `adamw` are the launches
+    micro_host = 0
+
+    def __init__(self, device, lr, betas, eps, weight_decay, max_grad_norm, schedule=None, skip_nonfinite=False, accum_steps=None, ema_decay=None,
+                 ema_warmup=True):
         if schedule is not None and not isinstance(schedule, LRSchedule):
             raise TypeError("optimizer controls: schedule must be an LRSchedule, got %r" % (schedule,))
-        buf = torch.zeros(2 * WORDS, device=device, dtype=torch.float32)
-        self.hyper, self.state = buf[:WORDS], buf[WORDS:]
+        windowed = accum_steps is not None or ema_decay is not None
+        buf = torch.zeros((3 if windowed else 2) * WORDS, device=device, dtype=torch.float32)
+        self.hyper, self.state = buf[:WORDS], buf[WORDS:2 * WORDS]
         if self.hyper.data_ptr() % 64 or self.state.data_ptr() % 64:
             raise RuntimeError("optimizer controls: the allocator returned a record that is not 64-byte aligned")
         self.schedule = schedule if schedule is not None else LRSchedule()
         self.skip_nonfinite = bool(skip_nonfinite)
         self._host = [None] * WORDS      # what the host last wrote into each word
         self.write(lr, betas, eps, weight_decay, max_grad_norm, 1.0)
+        if windowed:
+            self.window = buf[2 * WORDS:]
+            self._whost = [None] * WORDS
+            self.accum_steps, self.ema_decay, self.ema_warmup = 1, None, True
+            self.set_accum_steps(1 if accum_steps is None else accum_steps)
+            self.set_ema_decay(ema_decay, ema_warmup)
 
     # -- hyper ------------------------------------------------------------------------------------------------------------------
     def _put(self, idx, value):
@@ -175,7 +195,87 @@ class OptimControls:
         self.state[S_SKIPPED_TOTAL:S_SKIPPED_TOTAL + 1].fill_(float(total))
         self.state[S_SKIPPED_IN_A_ROW:S_SKIPPED_IN_A_ROW + 1].fill_(float(in_a_row))
 
+    # -- window ------------------------------------------------------------------------------------------------------------------
+    def _need_window(self, what):
+        if self.window is None:
+            raise RuntimeError("optimizer controls: %s needs the accumulation window (accum_steps= or ema_decay=)" % what)
+
+    def _wput(self, idx, value):
+        value = _f32(value)
+        if self._whost[idx] != value:
+            self.window[idx:idx + 1].fill_(value)
+            self._whost[idx] = value
+
+    def set_accum_steps(self, k):
+        """micro-steps per window; only between windows (the host's mirror of the window position must be 0: see `reset_window`)"""
+        self._need_window("set_accum_steps")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k < MAX_STEPS:
+            raise ValueError("optimizer controls: accum_steps must be a whole number in [1, 2^24), got %r" % (k,))
+        if self.micro_host != 0:
+            raise RuntimeError("optimizer controls: accum_steps cannot change inside a window (%d of %d micro-steps are held); finish the "
+                               "window or reset_window() first" % (self.micro_host, self.accum_steps))
+        self._wput(W_ACCUM_STEPS, float(k))
+        self.accum_steps = int(k)
+
+    def set_ema_decay(self, ema_decay, ema_warmup=None):
+        """d in [0, 1) (None: the record holds 0, no EMA slab is kept); ema_warmup: d_now = min(d, (1 + u) / (10 + u)) after u updates"""
+        self._need_window("set_ema_decay")
+        if ema_warmup is not None:
+            if not isinstance(ema_warmup, (bool, np.bool_)):
+                raise ValueError("optimizer controls: ema_warmup must be True or False, got %r" % (ema_warmup,))
+            self.ema_warmup = bool(ema_warmup)
+        d = 0.0 if ema_decay is None else _finite("ema_decay", ema_decay, 0.0, False, 1.0, True)
+        if _f32(d) >= 1.0:
+            raise ValueError("optimizer controls: ema_decay = %r rounds to 1 in fp32" % (ema_decay,))
+        self._wput(W_EMA_DECAY, d)
+        self._wput(W_EMA_WARMUP, 1.0 if self.ema_warmup else 0.0)
+        self.ema_decay = None if ema_decay is None else _f32(d)
+
+    def reset_window(self):
+        """drop the open window: a stream-ordered write of MICRO = 0, so the next `begin` zero-fills the gradient slab"""
+        self._need_window("reset_window")
+        self.window[W_MICRO:W_MICRO + 1].fill_(0.0)
+        self.micro_host = 0
+
+    def advance_mirror(self):
+        """one micro-step passed (called for every `prepare_accum` that is executed: eager here, per replay by the owner of a graph);
+        -> whether that micro-step closed its window"""
+        self.micro_host = (self.micro_host + 1) if self.micro_host + 1 < self.accum_steps else 0
+        return self.micro_host == 0
+
+    def closes_next(self):
+        """whether the next micro-step closes its window (host mirror)"""
+        return self.micro_host + 1 >= self.accum_steps
+
+    def wword(self, idx):
+        """0-dim fp32 view of a `window` word"""
+        self._need_window("wword")
+        return self.window[idx]
+
+    def window_counters(self):
+        """(micro, ema_updates) read back (one sync)"""
+        return float(self.window[W_MICRO]), float(self.window[W_EMA_UPDATES])
+
+    def load_window(self, ema_updates):
+        """the device half of the record as a checkpoint load leaves it: window position 0, the EMA update count as saved"""
+        self.window[W_MICRO:W_EMA_UPDATES].fill_(0.0)
+        self.window[W_EMA_UPDATES:W_EMA_UPDATES + 1].fill_(float(ema_updates))
+        self.micro_host = 0
+
     # -- launches ---------------------------------------------------------------------------------------------------------------
+    def begin(self, grad):
+        """zero the gradient slab if a window starts, else leave the partial sum (one kernel node)"""
+        check(lib.vptr_accum_begin(ptr(grad), grad.numel(), ptr(self.window), stream()), "vptr_accum_begin")
+
+    def prepare_accum(self, step_dev, sumsq_dev):
+        check(lib.vptr_optim_prepare_accum(ptr(self.hyper), ptr(self.state), ptr(self.window), ptr(step_dev), ptr(sumsq_dev), stream()),
+              "vptr_optim_prepare_accum")
+        if not torch.cuda.is_current_stream_capturing():
+            self.advance_mirror()
+
+    def adamw_ema(self, p, g, m, v, ema, n):
+        check(lib.vptr_adamw_ctl_ema(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), n, ptr(self.state), ptr(self.window), stream()), "vptr_adamw_ctl_ema")
+
     def prepare(self, step_dev, sumsq_dev):
         check(lib.vptr_optim_prepare(ptr(self.hyper), ptr(self.state), ptr(step_dev), ptr(sumsq_dev), stream()), "vptr_optim_prepare")
 

@@ -29,6 +29,7 @@ How the two stage-2 trainers are put together (`FARTrainer` subclasses `NARTrain
     uploads, capture, node census, instantiate), parameterised by the warm-up pass, the captured body, whether the weight-gradient tuning is
     waited for and settled, and whether a process group's watchdog thread runs beside the capture; `_replay` is the one replay prologue.
 """
+import contextlib
 import os
 import time
 
@@ -38,7 +39,7 @@ import torch.nn.functional as F
 from . import ops
 from ._lib import check, lib, ptr, stream
 from .model.criterion import GANLoss
-from .optim import S_GRAD_NORM, S_LR_NOW, S_SKIPPED_IN_A_ROW, S_SKIPPED_TOTAL, STATE_KEY, LRSchedule, OptimControls
+from .optim import S_GRAD_NORM, S_LR_NOW, S_SKIPPED_IN_A_ROW, S_SKIPPED_TOTAL, STATE_KEY, W_APPLY_NOW, W_MICRO, LRSchedule, OptimControls
 
 
 _HIP_NODE_TYPES = {0: "kernel", 1: "memcpy", 2: "memset", 3: "host", 4: "graph", 5: "empty", 6: "wait_event", 7: "event_record",
@@ -85,12 +86,23 @@ class FlatAdamW:
     assignment to `.lr`) rewrite with stream-ordered writes, so they also reach the next replay of a captured step; the rate follows the
     schedule on the device; with skip_nonfinite a step whose gradient norm is NaN or Inf leaves the parameters, both moments and the step
     count bit for bit as they were and is counted (`skipped()`, `skipped_in_a_row()`).  With a constant schedule the trajectory is
-    bit-identical to the uncontrolled optimizer's.  Without controls nothing changes: the same three launches, the same state_dict."""
+    bit-identical to the uncontrolled optimizer's.  Without controls nothing changes: the same three launches, the same state_dict.
+
+    accum_steps (a whole number k >= 1) / ema_decay (0 <= d < 1): either one switches the controls on as well and adds their `window`
+    record (include/vptr_hip_accum.h, csrc/accum.hip).  Every `zero_grad()` + backward + `step()` is then one MICRO-step: `zero_grad`
+    zeroes the gradient slab only when a window of k micro-steps starts, `step` issues the same launches every time, and the update
+    happens in the call that closes the window, on the sum of the window's gradients times grad_scale / k; the calls before it (holds)
+    leave parameters, moments, step count and schedule position bit for bit as they are.  `applied()` tells which kind a call was.
+    With ema_decay an EMA of the parameters (`ema`, laid out like `flat`, seeded with the parameters) is updated inside the update
+    kernel: ema += (1 - d_now) (p_new - ema), d_now = min(d, (1 + u) / (10 + u)) after u updates with ema_warmup, else d.  The default
+    accum_steps=None is k = 1 without the window record."""
 
     ctl = None   # optim.OptimControls when the controls are on
+    ema = None   # the EMA slab (ema_decay=)
+    _windowed = False
 
     def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, channel_last=(), schedule=None,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, accum_steps=None, ema_decay=None, ema_warmup=True):
         """channel_last: ids of [C, ...] parameters that the kernels consume channel-last (the (C,H,W) LayerNorm affines and
         the depthwise 3x3 weights of MlpDWBN): they are STORED channel-last in the slab and exposed as a permuted view of
         their usual shape, so no per-step transposes of the parameter or its gradient remain (AdamW is elementwise, the
@@ -128,8 +140,13 @@ class FlatAdamW:
         self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
         self.step_dev = torch.zeros(1, device=dev, dtype=torch.float32)
         self.sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
-        if schedule is not None or skip_nonfinite:
-            self.ctl = OptimControls(dev, lr, betas, eps, weight_decay, max_grad_norm, schedule, skip_nonfinite)
+        self._windowed = accum_steps is not None or ema_decay is not None
+        if schedule is not None or skip_nonfinite or self._windowed:
+            self.ctl = OptimControls(dev, lr, betas, eps, weight_decay, max_grad_norm, schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup)
+        if ema_decay is not None:
+            self.ema = self.flat.clone()
+        if self._windowed:
+            self.grad._vptr_accumulates = True   # ops.flush_wgrads: one adder per destination and launch in deterministic mode
         ops.register_flat_slab(self.flat, self.grad)  # backward kernels accumulate weight gradients in place
         # P16 planes of every nn.Linear-shaped weight of the slab (forward operand and transposed input-gradient operand), rebuilt
         # by one launch after each step: the GEMMs then stage weights by DMA instead of splitting fp32 per tile (ops.WeightPlanes)
@@ -190,6 +207,59 @@ class FlatAdamW:
         """... since the last applied step (0-dim fp32 device view): a run that no longer recovers shows here"""
         return self._need_ctl("skipped_in_a_row").word(S_SKIPPED_IN_A_ROW)
 
+    # -- accumulation window and EMA -------------------------------------------------------------------------------------------
+    def _need_window(self, what):
+        if not self._windowed:
+            raise RuntimeError("FlatAdamW.%s needs accum_steps= or ema_decay=" % what)
+        return self.ctl
+
+    @property
+    def accum_steps(self):
+        return self.ctl.accum_steps if self._windowed else 1
+
+    def set_accum_steps(self, k):
+        """micro-steps per window from the next window on; raises inside a window (`reset_window()` drops it)"""
+        self._need_window("set_accum_steps").set_accum_steps(k)
+
+    def set_ema_decay(self, ema_decay):
+        if self.ema is None or ema_decay is None:
+            raise RuntimeError("FlatAdamW.set_ema_decay: the EMA slab exists only when the optimizer was built with ema_decay=, and stays then")
+        self.ctl.set_ema_decay(ema_decay)
+
+    def reset_window(self):
+        """drop the micro-steps held in the open window (stream-ordered, reaches the next replay too): the next `zero_grad` zero-fills.
+        A capture ends with the window wherever its warm-up steps left it; call this to start the first replay on a window boundary."""
+        self._need_window("reset_window").reset_window()
+
+    def applied(self):
+        """1 if the last `step` call closed a window with an update, 0 for a hold or a skipped close (0-dim fp32 device view)"""
+        return self._need_window("applied").wword(W_APPLY_NOW)
+
+    def micro(self):
+        """micro-steps held in the open window (0-dim fp32 device view; 0 after a close)"""
+        return self._need_window("micro").wword(W_MICRO)
+
+    def ema_param(self, i):
+        """the EMA of parameter i in its logical shape (a view of the EMA slab)"""
+        if self.ema is None:
+            raise RuntimeError("FlatAdamW.ema_param needs ema_decay=")
+        return self._logical(self.ema, i)
+
+    def swap_ema(self):
+        """exchange the parameter slab and the EMA slab in place (one launch) and rebuild the weight planes"""
+        if self.ema is None:
+            raise RuntimeError("FlatAdamW.swap_ema needs ema_decay=")
+        check(lib.vptr_slab_swap(ptr(self.flat), ptr(self.ema), self.flat.numel(), stream()), "vptr_slab_swap")
+        self._swapped = not self._swapped
+        if self.planes is not None:
+            self.planes.refresh()
+
+    _swapped = False   # the parameter slab currently holds the EMA (inside NARTrainer.ema_weights)
+
+    def _not_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError("FlatAdamW.%s: the parameter slab holds the EMA weights (inside ema_weights()); leave the context first" % what)
+
     # -- torch.optim.AdamW-compatible state (checkpoints of the reference carry `optimizer_T.state_dict()`) ------------------
     def _logical(self, slab, i):
         """view of parameter i's range of `slab` (m, v, ...) in the parameter's LOGICAL shape: channel-last stored parameters
@@ -200,11 +270,14 @@ class FlatAdamW:
         return slab[off:off + n].view(cl[0]).permute(cl[1])
 
     def state_dict(self):
+        self._not_swapped("state_dict")
         state = {}
         step = self.step_dev.detach().clone().reshape(())
         for i in range(len(self.params)):
             state[i] = {"step": step.clone(), "exp_avg": self._logical(self.m, i).contiguous().clone(),
                         "exp_avg_sq": self._logical(self.v, i).contiguous().clone()}
+            if self.ema is not None:   # an unknown key of a parameter's state travels through torch.optim.AdamW.load_state_dict as well
+                state[i]["ema"] = self._logical(self.ema, i).contiguous().clone()
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "params": list(range(len(self.params)))}
@@ -212,9 +285,14 @@ class FlatAdamW:
             total, in_a_row = self.ctl.counters()
             group[STATE_KEY] = {"schedule": self.ctl.schedule.to_dict(), "skip_nonfinite": self.ctl.skip_nonfinite,
                                 "skipped_total": total, "skipped_in_a_row": in_a_row}
+            if self._windowed:
+                micro, ema_updates = self.ctl.window_counters()
+                group[STATE_KEY].update(accum_steps=self.ctl.accum_steps, micro=micro, ema_decay=self.ctl.ema_decay, ema_warmup=self.ctl.ema_warmup,
+                                        ema_updates=ema_updates)
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
+        self._not_swapped("load_state_dict")
         groups = sd["param_groups"]
         ids = [i for g in groups for i in g["params"]]
         if len(ids) != len(self.params):
@@ -248,7 +326,32 @@ class FlatAdamW:
                 self.ctl.schedule = LRSchedule.from_dict(saved["schedule"])
                 self.ctl.load_counters(saved["skipped_total"], saved["skipped_in_a_row"])
             self.ctl.write(self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, self._last_scale)
+            if self._windowed:
+                self._load_window(sd, ids, saved or {})
         ops.invalidate_weight_planes()   # a checkpoint load usually rewrites the parameters too (possibly through .data)
+
+    def _load_window(self, sd, ids, saved):
+        """Loading always ends on a window boundary: a partial window's gradients are not part of a checkpoint, so resume is bit-exact
+        at window boundaries only.  The EMA comes from the checkpoint; a dict without it (torch.optim.AdamW, an optimizer without
+        ema_decay) seeds it again from the parameters as they are now -- load the model before the optimizer."""
+        self.ctl.load_window(0.0)
+        if "accum_steps" in saved:
+            self.ctl.set_accum_steps(int(saved["accum_steps"]))
+            if self.ema is not None and saved.get("ema_decay") is not None:
+                self.ctl.set_ema_decay(saved["ema_decay"], bool(saved["ema_warmup"]))
+        if saved.get("micro"):
+            import warnings
+            warnings.warn("FlatAdamW.load_state_dict: the checkpoint was saved inside an accumulation window; the %d micro-batch(es) it held "
+                          "are dropped and the next step starts a window" % int(saved["micro"]))
+        if self.ema is None:
+            return
+        with torch.no_grad():
+            if all(sd["state"].get(pid) is not None and "ema" in sd["state"][pid] for pid in ids):
+                for i, pid in enumerate(ids):
+                    self._logical(self.ema, i).copy_(sd["state"][pid]["ema"])
+                self.ctl.load_window(saved.get("ema_updates", 0.0))
+            else:
+                self.ema.copy_(self.flat)
 
     def close(self):
         """drop this optimizer's process-wide registrations (gradient-slab lookup, weight planes); also runs when it is collected"""
@@ -267,7 +370,10 @@ class FlatAdamW:
         if p0.grad is None or p0.grad.data_ptr() != self.grad.data_ptr():
             raise RuntimeError("FlatAdamW: a parameter lost its flat gradient view (do not use set_to_none=True)")
         ops.discard_wgrads()  # leftovers of a backward pass that raised must not leak into this step
-        self.grad.zero_()
+        if self._windowed:
+            self.ctl.begin(self.grad)   # zero-fills when a window starts, keeps the partial sum otherwise: one kernel node either way
+        else:
+            self.grad.zero_()
 
     def grad_norm(self):
         """global L2 norm of the (scaled) gradients of the last step (device tensor), as clip_grad_norm_ returns"""
@@ -279,7 +385,10 @@ class FlatAdamW:
     _sumsq_ws = None
 
     def step(self, grad_scale=1.0):
-        """grad_scale multiplies every gradient before clipping (e.g. 1 / accumulation steps)"""
+        """grad_scale multiplies every gradient before clipping (e.g. 1 / accumulation steps; with accum_steps=k the 1 / k is applied
+        here, on top of grad_scale).  With accum_steps / ema_decay every call issues sumsq -> prepare -> update -> plane refresh; a hold
+        behaves as a skipped step does: the update kernel returns at once and the planes are rebuilt from unchanged weights."""
+        self._not_swapped("step")
         n = self.flat.numel()
         self._last_scale = float(grad_scale)
         if ops.config.deterministic:   # fixed-order two-pass sum (no atomics): the clip coefficient is reproducible bit for bit
@@ -292,15 +401,21 @@ class FlatAdamW:
         if self.ctl is not None:
             # sumsq -> prepare (skip decision, step count, schedule, update scalars: one lane) -> the update reading them -> plane refresh.
             # A skipped step still refreshes the planes: they are rebuilt from unchanged weights.
-            self.ctl.set_grad_scale(grad_scale)
-            self.ctl.prepare(self.step_dev, self.sumsq)
+            if self._windowed:
+                self.ctl.set_grad_scale(grad_scale / self.ctl.accum_steps)
+                self.ctl.prepare_accum(self.step_dev, self.sumsq)
+            else:
+                self.ctl.set_grad_scale(grad_scale)
+                self.ctl.prepare(self.step_dev, self.sumsq)
         else:
             self.step_dev.add_(1.0)
         prof = ops.profiling.opt
         if prof is not None:   # bench.py's HBM roofline pass: HIP events on the launch stream around the optimizer's streaming kernels
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record()
-        if self.ctl is not None:
+        if self.ema is not None:
+            self.ctl.adamw_ema(self.flat, self.grad, self.m, self.v, self.ema, n)
+        elif self.ctl is not None:
             self.ctl.adamw(self.flat, self.grad, self.m, self.v, n)
         else:
             check(lib.vptr_adamw(ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v), n, self.lr, self.betas[0], self.betas[1],
@@ -333,14 +448,22 @@ class NARTrainer:
     """One stage-2 NAR training step; see module docstring.  `enc`/`dec` are frozen (eval), `transformer` trains."""
 
     def __init__(self, enc, dec, transformer, batch_size, lr=1e-4, max_grad_norm=1.0, lam_pc=0.1, process_group=None,
-                 bucket_mb=64, dec_weight_grads=True, disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False):
-        """schedule / skip_nonfinite: the device-resident optimizer controls of `FlatAdamW` (optim.py), given to the transformer's optimizer
+                 bucket_mb=64, dec_weight_grads=True, disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False,
+                 accum_steps=None, ema_decay=None, ema_warmup=True):
+        """accum_steps / ema_decay / ema_warmup: gradient accumulation and EMA weights of `FlatAdamW`.  Every `step()` call is then one
+        micro-step and also returns "applied" (1 when the call closed a window with an update); `trainer.opt.reset_window()` drops an
+        open window, e.g. after `capture`, which ends wherever its warm-up steps left the window.  Data parallel: the calls that hold
+        flush their weight gradients without any all-reduce, the closing call exchanges the summed slab as before.  `ema_weights()`,
+        `eval_step(..., weights="ema")`, `predict(..., weights="ema")` and `ema_state_dict()` use the EMA.  Not with the adversarial
+        branch (`disc=`): its discriminator steps inside the forward pass.
+
+        schedule / skip_nonfinite: the device-resident optimizer controls of `FlatAdamW` (optim.py), given to the transformer's optimizer
         and, with the adversarial branch, to the discriminator's alike.  `step` then also returns "lr" and "skipped" (and "skipped_D"), and
         `capture`, `capture_front`, `verify_graph` work as before: `trainer.opt.set_lr(...)` between replays changes the next update.  A
         skipped step leaves parameters, moments and step count untouched; it still refreshes the weight planes (from unchanged weights),
         still advances the dropout seed, and BatchNorm running statistics of the forward pass it belongs to have been updated already."""
         self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                          schedule, skip_nonfinite)
+                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup)
         # loss_name_list MSE / GDL(alpha=1) / BiPatchNCE(N, Tf, 8, 8, temperature 1.0) of train_NAR.py:176-179 run as the fused kernels of
         # csrc/losses.hip (ops.mse_gdl, ops.nce_loss): plain kernel launches only, so the step can live in a hipGraph (DESIGN.md section 6)
         self.nce_temperature = 1.0
@@ -350,8 +473,11 @@ class NARTrainer:
             self._bufsync = BufferSync(self.T, 0, process_group)   # DDP's per-forward broadcast of rank 0's BatchNorm statistics
 
     def _init_stage2(self, enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                     schedule, skip_nonfinite):
+                     schedule, skip_nonfinite, accum_steps=None, ema_decay=None, ema_warmup=True):
         """what both stage-2 recipes construct: frozen auto-encoder, optional adversarial branch, the transformer's flat-slab optimizer"""
+        if disc is not None and (ema_decay is not None or (accum_steps is not None and accum_steps != 1)):
+            raise ValueError("accum_steps > 1 / ema_decay are not available with the adversarial branch (disc=): the discriminator's "
+                             "update runs inside every forward pass and has no accumulation window")
         self.enc, self.dec, self.T = enc.eval(), dec.eval(), transformer
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
@@ -368,7 +494,8 @@ class NARTrainer:
         for mod in list(self.enc.modules()) + list(self.dec.modules()):
             mod._vptr_frozen = True  # never stepped here: packed conv weights / eval-BN folds are cached (ops.frozen_weights)
         self.opt = FlatAdamW(self.T.parameters(), lr=lr, max_grad_norm=max_grad_norm, channel_last=_channel_last_ids(self.T),
-                             schedule=schedule, skip_nonfinite=skip_nonfinite)
+                             schedule=schedule, skip_nonfinite=skip_nonfinite, accum_steps=accum_steps,
+                             ema_decay=ema_decay, ema_warmup=ema_warmup)
         self._bufsync = None
         self._graph = None
 
@@ -449,6 +576,11 @@ class NARTrainer:
         """whether the all-reduces are issued between the weight-gradient chunks (VPTR_DP_OVERLAP=0: one plain exchange after them)"""
         return os.environ.get("VPTR_DP_OVERLAP", "1") != "0"
 
+    def _holds_next(self):
+        """whether the next optimizer call leaves its accumulation window open (the host's mirror of the window position: it is
+        deterministic, because neither a hold nor a skipped close moves a window boundary)"""
+        return self.opt._windowed and not self.opt.ctl.closes_next()
+
     def _allreduce_grads(self):
         if not self._exchanges():
             return
@@ -464,6 +596,13 @@ class NARTrainer:
         been enqueued, the slab range below the next chunk's first destination is final and its all-reduce is issued
         asynchronously (RCCL runs it on its own stream), overlapping the next chunk's GEMM."""
         self._grad_scale = 1.0
+        if self._exchanges() and self._holds_next():
+            # a micro-step that leaves its window open: the slab is a partial sum no other rank needs yet.  The weight gradients are
+            # flushed in one grouped launch and nothing crosses the process group; the closing call exchanges the window's sum
+            loss.backward()
+            ops.flush_wgrads()
+            self._grad_scale = 1.0 / self.world
+            return
         if not (self._exchanges() and self._overlaps()):
             loss.backward()
             ops.flush_wgrads()  # no-op: the grouped weight-gradient launch already ran at the end of backward
@@ -573,6 +712,7 @@ class NARTrainer:
     def step(self, past, future, meters=None):
         """one train step (a replay when `capture` / `capture_front` ran); meters: a `meters.DeviceLossMeters` that receives the returned
         terms in one launch issued behind the step -- outside any captured graph, so the meter can be swapped per epoch"""
+        self.opt._not_swapped("step (NARTrainer.step)")
         out = self._step(past, future)
         if meters is not None:
             meters.update(out)
@@ -598,7 +738,10 @@ class NARTrainer:
             self._replay(self._front, self._static_past, self._static_future, past, future, bufsync=True)
             ops.requeue_wgrads(self._front_items)
             self._grad_scale = 1.0
-            if self._overlaps():
+            if self._exchanges() and self._holds_next():   # an open window: flush, no all-reduce (see `_backward_and_exchange`)
+                ops.flush_wgrads()
+                self._grad_scale = 1.0 / self.world
+            elif self._overlaps():
                 self._exchange_held_wgrads()
             else:
                 ops.flush_wgrads()
@@ -607,9 +750,13 @@ class NARTrainer:
             self._static_out["grad_norm"] = self.opt.grad_norm()
             if self.opt.ctl is not None:
                 self._static_out["lr"], self._static_out["skipped"] = self.opt.lr_now(), self.opt.skipped()
+            if self.opt._windowed:
+                self._static_out["applied"] = self.opt.applied()
             return self._static_out
         if self._graph is not None:
             self._replay(self._graph, self._static_past, self._static_future, past, future)
+            if self.opt._windowed:
+                self.opt.ctl.advance_mirror()   # the replay ran one captured prepare launch
             return self._static_out
         return self._step_impl(past, future)
 
@@ -734,7 +881,39 @@ class NARTrainer:
         terms["grad_norm"] = self.opt.grad_norm()
         if self.opt.ctl is not None:
             terms["lr"], terms["skipped"] = self.opt.lr_now(), self.opt.skipped()
+        if self.opt._windowed:
+            terms["applied"] = self.opt.applied()
         return terms
+
+    # -- EMA weights ------------------------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run what is inside on the EMA weights: the parameter slab and the EMA slab are exchanged in place (one launch) and the weight
+        planes rebuilt, and exchanged back on exit, also when the body raises.  A captured eval graph reads the slab by address, so
+        `eval_step` replays work unchanged.  `step()` and the optimizer's `state_dict()` raise inside."""
+        self.opt.swap_ema()
+        try:
+            yield self
+        finally:
+            self.opt.swap_ema()
+
+    def ema_state_dict(self):
+        """the transformer's `state_dict()` with the EMA in place of every trained parameter; buffers are copied as they are (BatchNorm
+        running statistics are not averaged)"""
+        if self.opt.ema is None:
+            raise RuntimeError("ema_state_dict needs ema_decay=")
+        index = {id(p): i for i, p in enumerate(self.opt.params)}
+        sd = {k: v.detach().clone() for k, v in self.T.state_dict().items()}
+        with torch.no_grad():
+            for name, p in self.T.named_parameters():
+                if id(p) in index and name in sd:
+                    sd[name] = self.opt.ema_param(index[id(p)]).contiguous().clone()
+        return sd
+
+    def _weights(self, weights):
+        if weights not in ("raw", "ema"):
+            raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
+        return self.ema_weights() if weights == "ema" else contextlib.nullcontext()
 
     # -- validation pass: the train_flag=False branch of single_iter (train_NAR.py:88-100, train_FAR.py:85-94) ------------------------
     _eval_graph = None
@@ -769,10 +948,17 @@ class NARTrainer:
             else:
                 ops._seed_scope[key] = scope
 
-    def eval_step(self, past, future, meters=None):
+    def eval_step(self, past, future, meters=None, weights="raw"):
         """One validation iteration: the terms of `step` minus grad_norm, as 0-dim device tensors.  After `capture_eval` a batch of the
         captured shapes is a replay of the eval graph; any other batch runs eagerly.  The next `step` puts the modules back into train
-        mode.  meters: as in `step`."""
+        mode.  meters: as in `step`.  weights="ema": this one call inside `ema_weights()`; the returned terms are then copies (a
+        replay's static outputs would be overwritten by the next one)."""
+        if weights != "raw":
+            with self._weights(weights):
+                out = {k: v.clone() for k, v in self.eval_step(past, future).items()}
+            if meters is not None:
+                meters.update(out)
+            return out
         g = self._eval_graph
         if g is not None and past.shape == self._eval_past.shape and future.shape == self._eval_future.shape:
             self._replay(g, self._eval_past, self._eval_future, past, future)
@@ -811,6 +997,10 @@ class NARTrainer:
              "buffers": [b.detach().clone() for b in module.buffers()]}
         if opt.ctl is not None:   # the controls' device-written record: last rate, skip counters, the update scalars
             s["ctl"] = opt.ctl.state.clone()
+        if opt._windowed:         # inside a window the gradient slab is state too; the window record and the host's mirror of its position
+            s["grad"], s["window"], s["micro_host"] = opt.grad.clone(), opt.ctl.window.clone(), opt.ctl.micro_host
+        if opt.ema is not None:
+            s["ema"] = opt.ema.clone()
         return s
 
     @staticmethod
@@ -820,6 +1010,11 @@ class NARTrainer:
             b.copy_(v)
         if "ctl" in s:
             opt.ctl.state.copy_(s["ctl"])
+        if "window" in s:
+            opt.grad.copy_(s["grad"]); opt.ctl.window[8:].copy_(s["window"][8:])   # the device's half; the host's words follow the setters
+            opt.ctl.micro_host = s["micro_host"]
+        if "ema" in s:
+            opt.ema.copy_(s["ema"])
 
     def _snapshot(self):
         snap = self._slab_state(self.opt, self.T)
@@ -903,10 +1098,11 @@ class NARTrainer:
                     "eager_last": runs["eager"][-1], "graph_last": runs["graph"][-1]}
 
     @torch.no_grad()
-    def predict(self, past):
-        """Inference: Enc -> NAR -> Dec (Test_VPTR.ipynb cell 5, one NAR round)."""
+    def predict(self, past, weights="raw"):
+        """Inference: Enc -> NAR -> Dec (Test_VPTR.ipynb cell 5, one NAR round).  weights="ema": inside `ema_weights()`."""
         self.T.eval()
-        return self.dec(self.T(self.enc(past)))
+        with self._weights(weights):
+            return self.dec(self.T(self.enc(past)))
 
 
 class FARTrainer(NARTrainer):
@@ -916,11 +1112,12 @@ class FARTrainer(NARTrainer):
     flat-slab optimizer, grouped weight gradients and data-parallel exchange with `NARTrainer`."""
 
     def __init__(self, enc, dec, transformer, lr=1e-4, max_grad_norm=1.0, process_group=None, bucket_mb=64, dec_weight_grads=True,
-                 disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False):
-        """schedule / skip_nonfinite: as in `NARTrainer`"""
+                 disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False, accum_steps=None, ema_decay=None,
+                 ema_warmup=True):
+        """schedule / skip_nonfinite / accum_steps / ema_decay / ema_warmup: as in `NARTrainer`"""
         # no BufferSync: the FAR transformer has no BatchNorm (LayerNorm conv-FFNs), nothing to broadcast per forward
         self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                          schedule, skip_nonfinite)
+                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup)
 
     def _encode(self, past, future):
         return self.enc(torch.cat([past, future[:, :-1]], dim=1)), None    # train_FAR.py:53-55
@@ -931,10 +1128,12 @@ class FARTrainer(NARTrainer):
         return l_gdl + l_mse, {"T_GDL": l_gdl, "T_MSE": l_mse}
 
     @torch.no_grad()
-    def predict(self, past, num_pred, kv_cache=False):
-        """Autoregressive test-phase rollout (train_FAR.py:103-125): see vptr_amd.inference.far_rollout (kv_cache: its KV-cached path)."""
+    def predict(self, past, num_pred, kv_cache=False, weights="raw"):
+        """Autoregressive test-phase rollout (train_FAR.py:103-125): see vptr_amd.inference.far_rollout (kv_cache: its KV-cached path).
+        weights="ema": inside `ema_weights()`."""
         from .inference import far_rollout
-        return far_rollout(self.enc, self.dec, self.T, past, num_pred, kv_cache=kv_cache)
+        with self._weights(weights):
+            return far_rollout(self.enc, self.dec, self.T, past, num_pred, kv_cache=kv_cache)
 
     rollout = predict
 
@@ -945,12 +1144,16 @@ class AETrainer:
     update: lam_gan * BCE(D(rec), 1) + MSE + GDL, Adam on Enc + Dec.  torch.optim.Adam(lr 2e-4, betas (0.5, 0.999)) is
     AdamW with weight_decay 0, so both optimizers are `FlatAdamW` slabs (no clipping in this stage)."""
 
-    def __init__(self, enc, dec, disc, lr=2e-4, lam_gan=0.01, betas=(0.5, 0.999), gan_mode="vanilla", schedule=None, skip_nonfinite=False):
+    def __init__(self, enc, dec, disc, lr=2e-4, lam_gan=0.01, betas=(0.5, 0.999), gan_mode="vanilla", schedule=None, skip_nonfinite=False,
+                 accum_steps=None, ema_decay=None):
         """schedule / skip_nonfinite: the device-resident optimizer controls of `FlatAdamW` (optim.py) for both optimizers; `step` then
         also returns "lr_G", "lr_D", "skipped_G", "skipped_D".  The two decisions are independent: a non-finite discriminator gradient
         skips the discriminator's update only.  A skipped step still advances the dropout seed and the BatchNorm running statistics of
         Enc, Dec and the discriminator, which the forward passes have written before the gradient exists: a non-finite INPUT therefore
         still reaches the running statistics (train-mode steps do not read them; an `eval_step` does)."""
+        if ema_decay is not None or (accum_steps is not None and accum_steps != 1):
+            raise ValueError("accum_steps > 1 / ema_decay are not available for the stage-1 step: its two optimizers alternate inside "
+                             "one iteration and have no accumulation window")
         self.enc, self.dec, self.disc = enc, dec, disc
         for m in (enc, dec, disc):
             for p in m.parameters():
