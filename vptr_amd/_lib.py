@@ -159,6 +159,12 @@ ACCUM_SIGNATURES = {
     "vptr_slab_swap": [P, P, L, P],
 }
 
+# reconstruction losses with temporal weights, L1 and a GDL exponent, declared in include/vptr_hip_loss.h (additive as well)
+LOSS_SIGNATURES = {
+    "vptr_recon_loss_fwd": [P, P, P, P, P, P, I, I, I, I, I, F, P],
+    "vptr_recon_loss_bwd": [P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -166,7 +172,7 @@ def _load():
             "vptr_amd: %s is missing. Build it with `python -m vptr_amd.build` (needs hipcc, gfx950). "
             "There is no CPU / PyTorch fallback for the VPTR hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()):
+    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.argtypes = argt
         fn.restype = c_int

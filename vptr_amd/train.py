@@ -38,7 +38,7 @@ import torch.nn.functional as F
 
 from . import ops
 from ._lib import check, lib, ptr, stream
-from .model.criterion import GANLoss
+from .model.criterion import GDL, GANLoss, L1Loss, MSELoss, temporal_weight_func
 from .optim import S_GRAD_NORM, S_LR_NOW, S_SKIPPED_IN_A_ROW, S_SKIPPED_TOTAL, STATE_KEY, W_APPLY_NOW, W_MICRO, LRSchedule, OptimControls
 
 
@@ -75,6 +75,140 @@ def _copy_into(dst, src):
 
 
 DP_CHUNKS = 4  # grouped weight-gradient launches per step when gradients are exchanged between ranks
+
+
+class ReconLoss:
+    """Configuration of a trainer's reconstruction loss (`recon=`): which point-wise criterion joins the total, the exponent of the
+    gradient-difference loss and the per-frame weights of either -- `MSELoss(temporal_weight)`, `L1Loss(temporal_weight)` and
+    `GDL(alpha, temporal_weight)` of model/criterion.py on the kernels of csrc/recon_loss.hip (`ops.recon_losses`).
+
+    point: "mse", "l1" or "mse+l1" (what the total contains; both values are always reported, the one outside the total gets no
+        gradient).  gdl_alpha: finite, >= 1 (the criterion class accepts less; its gradient is NaN at every tie).
+    temporal_weight: None, "exp" (`temporal_weight_func(T)` for the T the trainer's loss sees) or a 1-D tensor / sequence of T values.
+    gdl_temporal_weight: the same choices for the GDL; "same" (the default) reuses `temporal_weight`.
+    No `norm_dim`: the normalised variants stay with the torch classes."""
+    POINTS = ("mse", "l1", "mse+l1")
+    SAME = "same"
+
+    def __init__(self, point="mse", gdl_alpha=1.0, temporal_weight=None, gdl_temporal_weight=SAME):
+        if point not in self.POINTS:
+            raise ValueError("ReconLoss: point must be one of %s (got %r)" % (self.POINTS, point))
+        if isinstance(gdl_alpha, bool) or not isinstance(gdl_alpha, (int, float)) or not 1.0 <= float(gdl_alpha) < float("inf"):
+            raise ValueError("ReconLoss: gdl_alpha must be a finite number >= 1 (got %r)" % (gdl_alpha,))
+        self.point, self.gdl_alpha = point, float(gdl_alpha)
+        self.temporal_weight = self._spec(temporal_weight, "temporal_weight")
+        self.gdl_temporal_weight = self.temporal_weight if isinstance(gdl_temporal_weight, str) and gdl_temporal_weight == self.SAME \
+            else self._spec(gdl_temporal_weight, "gdl_temporal_weight")
+
+    @staticmethod
+    def _spec(w, name):
+        if w is None or (isinstance(w, str) and w == "exp"):
+            return w
+        if isinstance(w, str):
+            raise ValueError("ReconLoss: %s must be None, \"exp\" or a vector (got %r)" % (name, w))
+        w = torch.as_tensor(w).detach().to("cpu", torch.float32)
+        if w.dim() != 1 or w.numel() < 1 or not bool(torch.isfinite(w).all()):
+            raise ValueError("ReconLoss: %s must be a finite 1-D vector (got shape %s)" % (name, tuple(w.shape)))
+        return w.clone()
+
+    @property
+    def has_weights(self):
+        return self.temporal_weight is not None or self.gdl_temporal_weight is not None
+
+    @staticmethod
+    def resolve(w, T, name="temporal_weight"):
+        """the fp32 CPU vector of length T a weight specification stands for (None stays None); ValueError for another length"""
+        if w is None:
+            return None
+        if isinstance(w, str):
+            if T < 2:
+                raise ValueError("ReconLoss: %s \"exp\" needs at least two time indices (got T = %d)" % (name, T))
+            return temporal_weight_func(T).float()
+        w = ReconLoss._spec(w, name)
+        if w.numel() != T:
+            raise ValueError("ReconLoss: %s has %d entries, the loss sees %d time indices" % (name, w.numel(), T))
+        return w
+
+    def total(self, l_mse, l_l1):
+        """the point-wise part of the total"""
+        return l_mse if self.point == "mse" else (l_l1 if self.point == "l1" else l_mse + l_l1)
+
+    @classmethod
+    def from_criteria(cls, point_criterion, gdl_criterion=None):
+        """point_criterion: an `MSELoss`, an `L1Loss` or a pair of both (their temporal weights must then agree); gdl_criterion: a `GDL`
+        (None: alpha 1, no weights).  ValueError when a `norm_dim` is set."""
+        crits = list(point_criterion) if isinstance(point_criterion, (list, tuple)) else [point_criterion]
+        kinds = []
+        for c in crits:
+            if not isinstance(c, (MSELoss, L1Loss)):
+                raise ValueError("ReconLoss.from_criteria: %r is neither an MSELoss nor an L1Loss of vptr_amd.model.criterion" % (c,))
+            if c.norm_dim is not None:
+                raise ValueError("ReconLoss.from_criteria: norm_dim = %r is not available on the kernels" % (c.norm_dim,))
+            kinds.append("mse" if isinstance(c, MSELoss) else "l1")
+        if sorted(kinds) not in (["mse"], ["l1"], ["l1", "mse"]):
+            raise ValueError("ReconLoss.from_criteria: expected one MSELoss, one L1Loss or one of each (got %s)" % kinds)
+        w = crits[0].temporal_weight
+        for c in crits[1:]:
+            same = (w is None and c.temporal_weight is None) or (w is not None and c.temporal_weight is not None
+                                                                 and torch.equal(torch.as_tensor(w).cpu(), torch.as_tensor(c.temporal_weight).cpu()))
+            if not same:
+                raise ValueError("ReconLoss.from_criteria: the MSELoss and the L1Loss carry different temporal weights; the kernels apply one")
+        if gdl_criterion is not None and not isinstance(gdl_criterion, GDL):
+            raise ValueError("ReconLoss.from_criteria: %r is no GDL of vptr_amd.model.criterion" % (gdl_criterion,))
+        alpha = 1.0 if gdl_criterion is None else gdl_criterion.alpha
+        wg = None if gdl_criterion is None else gdl_criterion.temporal_weight
+        return cls("+".join(k for k in ("mse", "l1") if k in kinds), alpha, w, wg)
+
+    def __repr__(self):
+        def show(w):
+            return w if w is None or isinstance(w, str) else "tensor[%d]" % w.numel()
+        return "ReconLoss(point=%r, gdl_alpha=%g, temporal_weight=%s, gdl_temporal_weight=%s)" % (
+            self.point, self.gdl_alpha, show(self.temporal_weight), show(self.gdl_temporal_weight))
+
+
+class _ReconMixin:
+    """what the trainers share of `recon=`: the device weight buffers (owned here, read by address by every launch, also from inside a
+    captured graph) and the loss call"""
+    recon = None
+    _recon_w = None          # (w_point, w_gdl) device fp32 [T] or None each, built at the first step; _recon_T: their length
+
+    def _init_recon(self, recon):
+        if recon is not None and not isinstance(recon, ReconLoss):
+            raise ValueError("recon must be a vptr_amd.train.ReconLoss or None (got %r)" % (recon,))
+        self.recon, self._recon_w = recon, None
+
+    def _recon_weights(self, T, device):
+        if self._recon_w is None:
+            r = self.recon
+            wp, wg = ReconLoss.resolve(r.temporal_weight, T), ReconLoss.resolve(r.gdl_temporal_weight, T, "gdl_temporal_weight")
+            self._recon_w = tuple(None if w is None else w.to(device) for w in (wp, wg))
+            self._recon_T = T
+        elif self._recon_T != T:
+            raise ValueError("ReconLoss: the temporal weights were built for %d time indices, this step's loss sees %d" % (self._recon_T, T))
+        return self._recon_w
+
+    def _recon_losses(self, pred, target):
+        """-> (l_mse, l_l1, l_gdl, the point-wise part of the total)"""
+        wp, wg = self._recon_weights(pred.shape[1], pred.device) if self.recon.has_weights else (None, None)
+        l_mse, l_l1, l_gdl = ops.recon_losses(pred, target, wp, wg, self.recon.gdl_alpha)
+        return l_mse, l_l1, l_gdl, self.recon.total(l_mse, l_l1)
+
+    def set_temporal_weight(self, w, gdl=None):
+        """rewrite the temporal weights in place: w for the point-wise term, gdl for the GDL (None: w as well).  The copies are ordinary
+        stream-ordered copies into the buffers the launches read by address, so a captured step uses the new values from its next replay
+        on and its graph is untouched.  Only weights the trainer was constructed with can be rewritten (a launch without them holds NULL)."""
+        if self.recon is None or not self.recon.has_weights:
+            raise ValueError("set_temporal_weight: this trainer was constructed without temporal weights (recon=ReconLoss(temporal_weight=...))")
+        gdl = w if gdl is None else gdl
+        if self._recon_w is None:            # nothing launched yet: the configuration is all there is to change
+            r = self.recon
+            self.recon = ReconLoss(r.point, r.gdl_alpha, None if r.temporal_weight is None else w, None if r.gdl_temporal_weight is None else gdl)
+            return
+        if gdl is not w and self._recon_w[1] is None:
+            raise ValueError("set_temporal_weight: this trainer's GDL was constructed without temporal weights")
+        for buf, new, name in ((self._recon_w[0], w, "temporal_weight"), (self._recon_w[1], gdl, "gdl_temporal_weight")):
+            if buf is not None:
+                buf.copy_(ReconLoss.resolve(new, self._recon_T, name), non_blocking=False)
 
 
 class FlatAdamW:
@@ -444,13 +578,16 @@ def _channel_last_ids(transformer):
     return ids
 
 
-class NARTrainer:
+class NARTrainer(_ReconMixin):
     """One stage-2 NAR training step; see module docstring.  `enc`/`dec` are frozen (eval), `transformer` trains."""
 
     def __init__(self, enc, dec, transformer, batch_size, lr=1e-4, max_grad_norm=1.0, lam_pc=0.1, process_group=None,
                  bucket_mb=64, dec_weight_grads=True, disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False,
-                 accum_steps=None, ema_decay=None, ema_warmup=True):
-        """accum_steps / ema_decay / ema_warmup: gradient accumulation and EMA weights of `FlatAdamW`.  Every `step()` call is then one
+                 accum_steps=None, ema_decay=None, ema_warmup=True, recon=None):
+        """recon: a `ReconLoss` -- the frame loss then runs on `ops.recon_losses` (L1, a GDL exponent, temporal weights of length Tf), the
+        returned terms gain "T_L1", and `set_temporal_weight` rewrites the weights between steps or replays.  None: `ops.mse_gdl` as ever.
+
+        accum_steps / ema_decay / ema_warmup: gradient accumulation and EMA weights of `FlatAdamW`.  Every `step()` call is then one
         micro-step and also returns "applied" (1 when the call closed a window with an update); `trainer.opt.reset_window()` drops an
         open window, e.g. after `capture`, which ends wherever its warm-up steps left the window.  Data parallel: the calls that hold
         flush their weight gradients without any all-reduce, the closing call exchanges the summed slab as before.  `ema_weights()`,
@@ -464,6 +601,7 @@ class NARTrainer:
         still advances the dropout seed, and BatchNorm running statistics of the forward pass it belongs to have been updated already."""
         self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
                           schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup)
+        self._init_recon(recon)
         # loss_name_list MSE / GDL(alpha=1) / BiPatchNCE(N, Tf, 8, 8, temperature 1.0) of train_NAR.py:176-179 run as the fused kernels of
         # csrc/losses.hip (ops.mse_gdl, ops.nce_loss): plain kernel launches only, so the step can live in a hipGraph (DESIGN.md section 6)
         self.nce_temperature = 1.0
@@ -660,12 +798,17 @@ class NARTrainer:
 
     def losses(self, pred_frames, future, pred_feats, future_feats):
         """cal_lossT (train_NAR.py:32-47, 81-91): MSE + GDL on the frames, lam_pc * BiPatchNCE on the L2-normalised NCE projections"""
+        nce = self._nce_operands(pred_feats, future_feats)
+        l_mse, l_gdl = ops.mse_gdl(pred_frames, future)
+        l_pc = ops.nce_loss(*nce, self.nce_temperature)
+        return l_gdl + l_mse + self.lam_pc * l_pc, l_gdl, l_mse, l_pc
+
+    def _nce_operands(self, pred_feats, future_feats):
+        """-> the (g, p, frames, L) of ops.nce_loss: the NCE projections of the future and the predicted features, token-major"""
         a = self.T.NCE_projector(pred_feats.permute(0, 1, 3, 4, 2))      # (N, T, h, w, C): token-major memory
         b = self.T.NCE_projector(future_feats.permute(0, 1, 3, 4, 2))
         N, T, h, w, C = a.shape
-        l_mse, l_gdl = ops.mse_gdl(pred_frames, future)
-        l_pc = ops.nce_loss(b.reshape(-1, C), a.reshape(-1, C), N * T, h * w, self.nce_temperature)
-        return l_gdl + l_mse + self.lam_pc * l_pc, l_gdl, l_mse, l_pc
+        return b.reshape(-1, C), a.reshape(-1, C), N * T, h * w
 
     # -- the stage-2 iteration, sequenced once for train and eval; a recipe contributes `_encode` and `_loss_terms` ----------------------
     def _encode(self, past, future):
@@ -679,8 +822,13 @@ class NARTrainer:
 
     def _loss_terms(self, pred_frames, pred_feats, past, future, future_feats):
         """-> (the recipe's part of the loss, its terms by name)"""
-        loss, l_gdl, l_mse, l_pc = self.losses(pred_frames, future, pred_feats, future_feats)
-        return loss, {"T_GDL": l_gdl, "T_MSE": l_mse, "T_bpc": l_pc}
+        if self.recon is None:
+            loss, l_gdl, l_mse, l_pc = self.losses(pred_frames, future, pred_feats, future_feats)
+            return loss, {"T_GDL": l_gdl, "T_MSE": l_mse, "T_bpc": l_pc}
+        nce = self._nce_operands(pred_feats, future_feats)               # the launch order of `losses`: projections, frame loss, NCE
+        l_mse, l_l1, l_gdl, l_point = self._recon_losses(pred_frames, future)
+        l_pc = ops.nce_loss(*nce, self.nce_temperature)
+        return l_gdl + l_point + self.lam_pc * l_pc, {"T_GDL": l_gdl, "T_MSE": l_mse, "T_bpc": l_pc, "T_L1": l_l1}
 
     def _forward(self, past, future, train, front=False):
         """-> (loss, terms): encoder, transformer, decoder, discriminator terms, recipe loss terms, generator's adversarial term"""
@@ -1113,19 +1261,24 @@ class FARTrainer(NARTrainer):
 
     def __init__(self, enc, dec, transformer, lr=1e-4, max_grad_norm=1.0, process_group=None, bucket_mb=64, dec_weight_grads=True,
                  disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False, accum_steps=None, ema_decay=None,
-                 ema_warmup=True):
-        """schedule / skip_nonfinite / accum_steps / ema_decay / ema_warmup: as in `NARTrainer`"""
+                 ema_warmup=True, recon=None):
+        """schedule / skip_nonfinite / accum_steps / ema_decay / ema_warmup / recon: as in `NARTrainer`; the temporal weights of a
+        `ReconLoss` have Tp - 1 + Tf entries here, one per frame of cat(past[:, 1:], future)"""
         # no BufferSync: the FAR transformer has no BatchNorm (LayerNorm conv-FFNs), nothing to broadcast per forward
         self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
                           schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup)
+        self._init_recon(recon)
 
     def _encode(self, past, future):
         return self.enc(torch.cat([past, future[:, :-1]], dim=1)), None    # train_FAR.py:53-55
 
     def _loss_terms(self, pred_frames, pred_feats, past, future, aux):
         real = torch.cat([past[:, 1:], future], dim=1)                       # :80
-        l_mse, l_gdl = ops.mse_gdl(pred_frames, real)                        # cal_lossT :32-46
-        return l_gdl + l_mse, {"T_GDL": l_gdl, "T_MSE": l_mse}
+        if self.recon is None:
+            l_mse, l_gdl = ops.mse_gdl(pred_frames, real)                    # cal_lossT :32-46
+            return l_gdl + l_mse, {"T_GDL": l_gdl, "T_MSE": l_mse}
+        l_mse, l_l1, l_gdl, l_point = self._recon_losses(pred_frames, real)
+        return l_gdl + l_point, {"T_GDL": l_gdl, "T_MSE": l_mse, "T_L1": l_l1}
 
     @torch.no_grad()
     def predict(self, past, num_pred, kv_cache=False, weights="raw"):
@@ -1138,15 +1291,18 @@ class FARTrainer(NARTrainer):
     rollout = predict
 
 
-class AETrainer:
+class AETrainer(_ReconMixin):
     """One stage-1 step (`single_iter` of train_AutoEncoder.py:44-78): rec = Dec(Enc(cat(past, future))) with train-mode
     BatchNorm; discriminator update on (rec.detach(), x): 0.5 * lam_gan * (BCE(D(fake), 0) + BCE(D(real), 1)), Adam; generator
     update: lam_gan * BCE(D(rec), 1) + MSE + GDL, Adam on Enc + Dec.  torch.optim.Adam(lr 2e-4, betas (0.5, 0.999)) is
     AdamW with weight_decay 0, so both optimizers are `FlatAdamW` slabs (no clipping in this stage)."""
 
     def __init__(self, enc, dec, disc, lr=2e-4, lam_gan=0.01, betas=(0.5, 0.999), gan_mode="vanilla", schedule=None, skip_nonfinite=False,
-                 accum_steps=None, ema_decay=None):
-        """schedule / skip_nonfinite: the device-resident optimizer controls of `FlatAdamW` (optim.py) for both optimizers; `step` then
+                 accum_steps=None, ema_decay=None, recon=None):
+        """recon: a `ReconLoss` with `point` and `gdl_alpha` only (the stage-1 loss has no time axis to weight: temporal weights raise
+        ValueError); `step` and `eval_step` then also return "AE_L1".
+
+        schedule / skip_nonfinite: the device-resident optimizer controls of `FlatAdamW` (optim.py) for both optimizers; `step` then
         also returns "lr_G", "lr_D", "skipped_G", "skipped_D".  The two decisions are independent: a non-finite discriminator gradient
         skips the discriminator's update only.  A skipped step still advances the dropout seed and the BatchNorm running statistics of
         Enc, Dec and the discriminator, which the forward passes have written before the gradient exists: a non-finite INPUT therefore
@@ -1154,6 +1310,9 @@ class AETrainer:
         if ema_decay is not None or (accum_steps is not None and accum_steps != 1):
             raise ValueError("accum_steps > 1 / ema_decay are not available for the stage-1 step: its two optimizers alternate inside "
                              "one iteration and have no accumulation window")
+        self._init_recon(recon)
+        if recon is not None and recon.has_weights:
+            raise ValueError("AETrainer: temporal weights are not available for the stage-1 loss (ReconLoss point and gdl_alpha only)")
         self.enc, self.dec, self.disc = enc, dec, disc
         for m in (enc, dec, disc):
             for p in m.parameters():
@@ -1167,6 +1326,14 @@ class AETrainer:
     def has_graph(self, train=True):
         """the stage-1 step is not captured"""
         return False
+
+    def _ae_recon(self, rec, x):
+        """-> (l_mse, l_gdl, the point-wise part of the total, further terms by name)"""
+        if self.recon is None:
+            l_mse, l_gdl = ops.mse_gdl(rec, x)
+            return l_mse, l_gdl, l_mse, {}
+        l_mse, l_l1, l_gdl, l_point = self._recon_losses(rec, x)
+        return l_mse, l_gdl, l_point, {"AE_L1": l_l1}
 
     def step(self, past, future, meters=None):
         out = self._step(past, future)
@@ -1188,9 +1355,10 @@ class AETrainer:
         l_fake = self.gan(self.disc(rec.flatten(0, 1)), False)
         l_real = self.gan(self.disc(x.flatten(0, 1)), True)
         l_gan = self.gan(self.disc(rec.flatten(0, 1)), True)
-        l_mse, l_gdl = ops.mse_gdl(rec, x)
-        out = {"AEgan": l_gan, "AE_MSE": l_mse, "AE_GDL": l_gdl, "AE_total": self.lam_gan * l_gan + l_mse + l_gdl,
+        l_mse, l_gdl, l_point, extra = self._ae_recon(rec, x)
+        out = {"AEgan": l_gan, "AE_MSE": l_mse, "AE_GDL": l_gdl, "AE_total": self.lam_gan * l_gan + l_point + l_gdl,
                "Dtotal": (l_fake + l_real) * 0.5 * self.lam_gan, "Dfake": l_fake, "Dreal": l_real}
+        out.update(extra)
         if meters is not None:
             meters.update(out)
         return out
@@ -1218,12 +1386,13 @@ class AETrainer:
         for p in self.disc.parameters():
             p.requires_grad_(False)
         l_gan = self.gan(self.disc(rec.flatten(0, 1)), True)
-        l_mse, l_gdl = ops.mse_gdl(rec, x)
-        loss_G = self.lam_gan * l_gan + l_mse + l_gdl
+        l_mse, l_gdl, l_point, extra = self._ae_recon(rec, x)
+        loss_G = self.lam_gan * l_gan + l_point + l_gdl
         loss_G.backward()
         self.opt_G.step()
         out = {"AEgan": l_gan.detach(), "AE_MSE": l_mse.detach(), "AE_GDL": l_gdl.detach(), "AE_total": loss_G.detach(),
                "Dtotal": loss_D.detach(), "Dfake": l_fake.detach(), "Dreal": l_real.detach()}
+        out.update({k: v.detach() for k, v in extra.items()})
         if self.opt_G.ctl is not None:
             out.update(lr_G=self.opt_G.lr_now(), lr_D=self.opt_D.lr_now(), skipped_G=self.opt_G.skipped(), skipped_D=self.opt_D.skipped())
         return out
