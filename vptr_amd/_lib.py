@@ -164,6 +164,11 @@ LOSS_SIGNATURES = {
     "vptr_recon_loss_fwd": [P, P, P, P, P, P, I, I, I, I, I, F, P],
     "vptr_recon_loss_bwd": [P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
 }
+# adversarial losses (vanilla / lsgan / wgangp) for one tensor or a discriminator pair, declared in include/vptr_hip_gan.h (additive as well)
+GAN_SIGNATURES = {
+    "vptr_gan_loss_fwd": [P, L, L, I, P, L, L, I, I, F, F, F, P, P, P],
+    "vptr_gan_loss_bwd": [P, L, L, I, P, P, L, L, I, P, I, F, F, F, P, P, P, P],
+}
 
 
 def _load():
@@ -172,7 +177,7 @@ def _load():
             "vptr_amd: %s is missing. Build it with `python -m vptr_amd.build` (needs hipcc, gfx950). "
             "There is no CPU / PyTorch fallback for the VPTR hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()):
+    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(GAN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.argtypes = argt
         fn.restype = c_int

@@ -54,7 +54,7 @@ from .conv import (  # noqa: F401
     wino_resnet_blocks, _Conv2dNHWCFn, conv2d_nhwc, _Conv7InFn, conv7_in, _Conv7OutFn, conv7_out, bn_fold,
 )
 from .losses import (  # noqa: F401
-    _MseGdlFn, mse_gdl, _ReconLossFn, recon_losses, _NceFn, nce_loss,
+    _MseGdlFn, mse_gdl, _ReconLossFn, recon_losses, _GanLossFn, GAN_MODES, gan_loss, gan_loss_pair, _NceFn, nce_loss,
 )
 from .metrics import (  # noqa: F401
     FRAME_METRICS_BAND, FRAME_METRICS_MAX_W, frame_metrics,

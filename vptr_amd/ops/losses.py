@@ -1,4 +1,4 @@
-"""Fused loss kernels: MSE + GDL, the reconstruction losses with temporal weights / L1 / a GDL exponent, BiPatchNCE."""
+"""Fused loss kernels: MSE + GDL, the reconstruction losses with temporal weights / L1 / a GDL exponent, the adversarial losses, BiPatchNCE."""
 
 import torch
 
@@ -109,6 +109,96 @@ def recon_losses(pred, gt, w_point=None, w_gdl=None, gdl_alpha=1.0, time_dim=1):
         ppf *= s
     w_point, w_gdl = _time_weight(w_point, "w_point", T, pred.device), _time_weight(w_gdl, "w_gdl", T, pred.device)
     return _ReconLossFn.apply(_c(pred), _c(gt), w_point, w_gdl, alpha, ppf, T)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# adversarial losses (csrc/gan_loss.hip, include/vptr_hip_gan.h): GANLoss of model/criterion.py as fixed-order kernels
+# ------------------------------------------------------------------------------------------------------------------
+GAN_MODES = {"vanilla": 0, "lsgan": 1, "wgangp": 2}
+GAN_CHUNK = 2048   # elements per forward workgroup: the scratch holds one float per chunk of each tensor
+
+
+def _elem_stride(t):
+    """the one stride (in elements) between consecutive logical elements of t, or None when t has no such stride: a contiguous tensor
+    gives 1, a channel slice y[:, :1] of a [R, 4] buffer gives 4"""
+    dims = [(n, s) for n, s in zip(t.shape, t.stride()) if n != 1]
+    if not dims:
+        return 1
+    for (_, s), (n1, s1) in zip(dims[:-1], dims[1:]):
+        if s != s1 * n1:
+            return None
+    return dims[-1][1] if dims[-1][1] >= 1 else None
+
+
+def _gan_operand(x, name):
+    """-> (the tensor the kernel reads in place, its element stride)"""
+    if x.dtype != torch.float32:
+        raise RuntimeError("%s: fp32 logits expected (got %s)" % (name, x.dtype))
+    if x.numel() < 1:
+        raise RuntimeError("%s: at least one logit expected (got shape %s)" % (name, tuple(x.shape)))
+    s = _elem_stride(x)
+    return (x, s) if s is not None else (x.contiguous(), 1)
+
+
+def _gan_cfg(name, mode, real_label, fake_label, coef=1.0):
+    if mode not in GAN_MODES:
+        raise ValueError("%s: mode must be one of %s (got %r)" % (name, sorted(GAN_MODES), mode))
+    vals = tuple(float(v) for v in (real_label, fake_label, coef))
+    if any(v != v or v in (float("inf"), float("-inf")) for v in vals):
+        raise ValueError("%s: real_label, fake_label and coef must be finite (got %r)" % (name, vals))
+    return (GAN_MODES[mode],) + vals
+
+
+class _GanLossFn(torch.autograd.Function):
+    """GANLoss(mode)(xa, a_is_real) -- and, with an xb, GANLoss(mode)(xb, b_is_real) and coef * (their sum) -- in two launches forward
+    and ONE elementwise launch backward that takes the upstream gradients of the three outputs as device scalars and forms
+    (g + coef * g_total) / n in the kernel.  An output nobody differentiates hands the backward no tensor
+    (set_materialize_grads(False)): its scalar is NULL = 0."""
+
+    @staticmethod
+    def forward(ctx, xa, sa, a_is_real, xb, sb, b_is_real, cfg):
+        mode, real_label, fake_label, coef = cfg
+        na, nb = xa.numel(), (0 if xb is None else xb.numel())
+        scratch = torch.empty(-(-na // GAN_CHUNK) - (-nb // GAN_CHUNK), device=xa.device, dtype=torch.float32)
+        out3 = torch.empty(3, device=xa.device, dtype=torch.float32)
+        check(lib.vptr_gan_loss_fwd(ptr(xa), na, sa, int(a_is_real), ptr(xb), nb, sb, int(b_is_real), mode, real_label, fake_label, coef,
+                                    ptr(scratch), ptr(out3), stream()), "vptr_gan_loss_fwd")
+        ctx.save_for_backward(xa, xb)
+        ctx.cfg = (sa, int(a_is_real), sb, int(b_is_real)) + cfg
+        ctx.set_materialize_grads(False)
+        la, lb, total = out3.unbind(0)
+        return la, lb, total
+
+    @staticmethod
+    def backward(ctx, g_a, g_b, g_total):
+        xa, xb = ctx.saved_tensors
+        sa, a_is_real, sb, b_is_real, mode, real_label, fake_label, coef = ctx.cfg
+        dxa = torch.empty(xa.shape, device=xa.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        dxb = torch.empty(xb.shape, device=xb.device, dtype=torch.float32) if (xb is not None and ctx.needs_input_grad[3]) else None
+        gs = [None if g is None else _c(g) for g in (g_a, g_b, g_total)]
+        check(lib.vptr_gan_loss_bwd(ptr(xa), xa.numel(), sa, a_is_real, ptr(dxa), ptr(xb), 0 if xb is None else xb.numel(), sb, b_is_real, ptr(dxb),
+                                    mode, real_label, fake_label, coef, ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), stream()), "vptr_gan_loss_bwd")
+        return dxa, None, None, dxb, None, None, None
+
+
+def gan_loss(logits, target_is_real, mode="vanilla", real_label=1.0, fake_label=0.0):
+    """-> 0-dim device tensor: GANLoss(mode, real_label, fake_label)(logits, target_is_real) of model/criterion.py.  A contiguous tensor,
+    or a view with one uniform element stride such as y[:, :1], is read in place; anything else is made contiguous first."""
+    _lib.require_cuda(logits)
+    cfg = _gan_cfg("gan_loss", mode, real_label, fake_label)
+    x, s = _gan_operand(logits, "gan_loss")
+    return _GanLossFn.apply(x, s, bool(target_is_real), None, 1, False, cfg)[0]
+
+
+def gan_loss_pair(fake_logits, real_logits, coef, mode="vanilla", real_label=1.0, fake_label=0.0):
+    """-> (l_fake, l_real, total) 0-dim device tensors of one discriminator update: l_fake = GANLoss(mode)(fake_logits, False), l_real =
+    GANLoss(mode)(real_logits, True), total = coef * (l_fake + l_real), formed on the device (cal_lossD: coef = 0.5 * lam_gan).  The two
+    tensors may differ in size; each is read in place under the rule of `gan_loss`."""
+    _lib.require_cuda(fake_logits, real_logits)
+    cfg = _gan_cfg("gan_loss_pair", mode, real_label, fake_label, coef)
+    xa, sa = _gan_operand(fake_logits, "gan_loss_pair")
+    xb, sb = _gan_operand(real_logits, "gan_loss_pair")
+    return _GanLossFn.apply(xa, sa, False, xb, sb, True, cfg)
 
 
 class _NceFn(torch.autograd.Function):

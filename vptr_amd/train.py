@@ -211,6 +211,30 @@ class _ReconMixin:
                 buf.copy_(ReconLoss.resolve(new, self._recon_T, name), non_blocking=False)
 
 
+class _GanMixin:
+    """How the trainers evaluate the adversarial loss: the torch `GANLoss` module (`gan_loss="torch"`, the default) or the fixed-order
+    kernels of csrc/gan_loss.hip (`gan_loss="fused"`).  `self.gan`, the criterion module with labels 1 / 0, is built by the trainer in
+    both settings; the fused calls take the same `gan_mode` and the same labels."""
+    gan_fused = False
+
+    def _init_gan_loss(self, gan_loss, gan_mode):
+        if gan_loss not in ("torch", "fused"):
+            raise ValueError("gan_loss must be 'torch' or 'fused', got %r" % (gan_loss,))
+        if gan_loss == "fused" and gan_mode not in ops.GAN_MODES:
+            raise ValueError("gan_loss='fused': gan_mode must be one of %s, got %r" % (sorted(ops.GAN_MODES), gan_mode))
+        self.gan_loss, self.gan_mode, self.gan_fused = gan_loss, gan_mode, gan_loss == "fused"
+
+    def _gan_pair(self, fake_logits, real_logits):
+        """fused cal_lossD -> (l_fake, l_real, 0.5 * lam_gan * (l_fake + l_real)) in one forward call"""
+        return ops.gan_loss_pair(fake_logits, real_logits, 0.5 * self.lam_gan, mode=self.gan_mode, real_label=1.0, fake_label=0.0)
+
+    def _gan_term(self, logits):
+        """the generator's adversarial term: the logits of generated frames against the real label"""
+        if self.gan_fused:
+            return ops.gan_loss(logits, True, mode=self.gan_mode, real_label=1.0, fake_label=0.0)
+        return self.gan(logits, True)
+
+
 class FlatAdamW:
     """torch.optim.AdamW semantics (lr, betas, eps, decoupled weight decay, bias correction) on one flat slab, with
     clip_grad_norm_ folded in.  Every parameter must receive a gradient each step (true for the VPTR transformers).
@@ -578,14 +602,18 @@ def _channel_last_ids(transformer):
     return ids
 
 
-class NARTrainer(_ReconMixin):
+class NARTrainer(_ReconMixin, _GanMixin):
     """One stage-2 NAR training step; see module docstring.  `enc`/`dec` are frozen (eval), `transformer` trains."""
 
     def __init__(self, enc, dec, transformer, batch_size, lr=1e-4, max_grad_norm=1.0, lam_pc=0.1, process_group=None,
                  bucket_mb=64, dec_weight_grads=True, disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False,
-                 accum_steps=None, ema_decay=None, ema_warmup=True, recon=None):
+                 accum_steps=None, ema_decay=None, ema_warmup=True, recon=None, gan_loss="torch"):
         """recon: a `ReconLoss` -- the frame loss then runs on `ops.recon_losses` (L1, a GDL exponent, temporal weights of length Tf), the
         returned terms gain "T_L1", and `set_temporal_weight` rewrites the weights between steps or replays.  None: `ops.mse_gdl` as ever.
+
+        gan_loss: "torch" (the `GANLoss` module: ATen expand, BCE, mean and their autograd) or "fused" (`ops.gan_loss_pair` for the
+        discriminator update with coef = 0.5 * lam_gan, `ops.gan_loss` for the generator term: csrc/gan_loss.hip, fixed-order kernels in
+        the `gan_mode` given).  The returned keys are the same; without a discriminator the setting is only validated.
 
         accum_steps / ema_decay / ema_warmup: gradient accumulation and EMA weights of `FlatAdamW`.  Every `step()` call is then one
         micro-step and also returns "applied" (1 when the call closed a window with an update); `trainer.opt.reset_window()` drops an
@@ -600,7 +628,7 @@ class NARTrainer(_ReconMixin):
         skipped step leaves parameters, moments and step count untouched; it still refreshes the weight planes (from unchanged weights),
         still advances the dropout seed, and BatchNorm running statistics of the forward pass it belongs to have been updated already."""
         self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup)
+                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup, gan_loss)
         self._init_recon(recon)
         # loss_name_list MSE / GDL(alpha=1) / BiPatchNCE(N, Tf, 8, 8, temperature 1.0) of train_NAR.py:176-179 run as the fused kernels of
         # csrc/losses.hip (ops.mse_gdl, ops.nce_loss): plain kernel launches only, so the step can live in a hipGraph (DESIGN.md section 6)
@@ -611,7 +639,7 @@ class NARTrainer(_ReconMixin):
             self._bufsync = BufferSync(self.T, 0, process_group)   # DDP's per-forward broadcast of rank 0's BatchNorm statistics
 
     def _init_stage2(self, enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                     schedule, skip_nonfinite, accum_steps=None, ema_decay=None, ema_warmup=True):
+                     schedule, skip_nonfinite, accum_steps=None, ema_decay=None, ema_warmup=True, gan_loss="torch"):
         """what both stage-2 recipes construct: frozen auto-encoder, optional adversarial branch, the transformer's flat-slab optimizer"""
         if disc is not None and (ema_decay is not None or (accum_steps is not None and accum_steps != 1)):
             raise ValueError("accum_steps > 1 / ema_decay are not available with the adversarial branch (disc=): the discriminator's "
@@ -620,7 +648,7 @@ class NARTrainer(_ReconMixin):
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.bucket_elems = bucket_mb * (1 << 20) // 4
-        self._init_gan(disc, lam_gan, lr, gan_mode, schedule, skip_nonfinite)
+        self._init_gan(disc, lam_gan, lr, gan_mode, schedule, skip_nonfinite, gan_loss)
         # Stage 2 optimises the transformer only (train_NAR.py:205).  The reference nevertheless leaves the decoder's
         # parameters trainable (train_NAR.py:190-191, train_FAR.py:181-182), so its backward computes decoder weight gradients nobody
         # consumes; that work is reproduced by default (dec_weight_grads=True) so that the measured step does everything the reference's does.
@@ -641,8 +669,9 @@ class NARTrainer(_ReconMixin):
     _front_items = ()
 
     # -- optional adversarial branch (train_NAR.py:22-30,37-41,66-79; train_FAR.py:22-45,66-80): off in the reference scripts ----
-    def _init_gan(self, disc, lam_gan, lr, gan_mode, schedule=None, skip_nonfinite=False):
+    def _init_gan(self, disc, lam_gan, lr, gan_mode, schedule=None, skip_nonfinite=False, gan_loss="torch"):
         self.disc, self.lam_gan = disc, lam_gan
+        self._init_gan_loss(gan_loss, gan_mode)
         if disc is None:
             return
         if lam_gan is None:
@@ -660,9 +689,12 @@ class NARTrainer(_ReconMixin):
         for p in self.disc.parameters():
             p.requires_grad_(True)
         self.opt_D.zero_grad()
-        l_fake = self.gan(self.disc(fake.detach().flatten(0, 1)), False)
-        l_real = self.gan(self.disc(real.flatten(0, 1)), True)
-        loss_D = (l_fake + l_real) * 0.5 * self.lam_gan
+        if self.gan_fused:
+            l_fake, l_real, loss_D = self._gan_pair(self.disc(fake.detach().flatten(0, 1)), self.disc(real.flatten(0, 1)))
+        else:
+            l_fake = self.gan(self.disc(fake.detach().flatten(0, 1)), False)
+            l_real = self.gan(self.disc(real.flatten(0, 1)), True)
+            loss_D = (l_fake + l_real) * 0.5 * self.lam_gan
         loss_D.backward()
         if self.pg is not None and self.world > 1:   # the reference's DDP-wrapped discriminator averages its gradients too
             ops.flush_wgrads()
@@ -849,7 +881,7 @@ class NARTrainer(_ReconMixin):
             extra = self._disc_update(pred_frames, future) if train else self._eval_disc(pred_frames, future)
         loss, terms = self._loss_terms(pred_frames, pred_feats, past, future, aux)
         if self.disc is not None:
-            extra["T_gan"] = self.gan(self.disc(pred_frames.flatten(0, 1)), True)
+            extra["T_gan"] = self._gan_term(self.disc(pred_frames.flatten(0, 1)))
             loss = loss + self.lam_gan * extra["T_gan"]
         return loss, dict({"T_total": loss}, **terms, **extra)
 
@@ -1068,6 +1100,9 @@ class NARTrainer(_ReconMixin):
 
     def _eval_disc(self, fake, real):
         """cal_lossD, forward only (eval-mode discriminator): both clips flattened to frames, whatever their lengths"""
+        if self.gan_fused:
+            l_fake, l_real, l_D = self._gan_pair(self.disc(fake.flatten(0, 1)), self.disc(real.flatten(0, 1)))
+            return {"Dtotal": l_D, "Dfake": l_fake, "Dreal": l_real}
         l_fake = self.gan(self.disc(fake.flatten(0, 1)), False)
         l_real = self.gan(self.disc(real.flatten(0, 1)), True)
         return {"Dtotal": (l_fake + l_real) * 0.5 * self.lam_gan, "Dfake": l_fake, "Dreal": l_real}
@@ -1261,12 +1296,12 @@ class FARTrainer(NARTrainer):
 
     def __init__(self, enc, dec, transformer, lr=1e-4, max_grad_norm=1.0, process_group=None, bucket_mb=64, dec_weight_grads=True,
                  disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False, accum_steps=None, ema_decay=None,
-                 ema_warmup=True, recon=None):
-        """schedule / skip_nonfinite / accum_steps / ema_decay / ema_warmup / recon: as in `NARTrainer`; the temporal weights of a
+                 ema_warmup=True, recon=None, gan_loss="torch"):
+        """schedule / skip_nonfinite / accum_steps / ema_decay / ema_warmup / recon / gan_loss: as in `NARTrainer`; the temporal weights of a
         `ReconLoss` have Tp - 1 + Tf entries here, one per frame of cat(past[:, 1:], future)"""
         # no BufferSync: the FAR transformer has no BatchNorm (LayerNorm conv-FFNs), nothing to broadcast per forward
         self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup)
+                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup, gan_loss)
         self._init_recon(recon)
 
     def _encode(self, past, future):
@@ -1291,16 +1326,19 @@ class FARTrainer(NARTrainer):
     rollout = predict
 
 
-class AETrainer(_ReconMixin):
+class AETrainer(_ReconMixin, _GanMixin):
     """One stage-1 step (`single_iter` of train_AutoEncoder.py:44-78): rec = Dec(Enc(cat(past, future))) with train-mode
     BatchNorm; discriminator update on (rec.detach(), x): 0.5 * lam_gan * (BCE(D(fake), 0) + BCE(D(real), 1)), Adam; generator
     update: lam_gan * BCE(D(rec), 1) + MSE + GDL, Adam on Enc + Dec.  torch.optim.Adam(lr 2e-4, betas (0.5, 0.999)) is
     AdamW with weight_decay 0, so both optimizers are `FlatAdamW` slabs (no clipping in this stage)."""
 
     def __init__(self, enc, dec, disc, lr=2e-4, lam_gan=0.01, betas=(0.5, 0.999), gan_mode="vanilla", schedule=None, skip_nonfinite=False,
-                 accum_steps=None, ema_decay=None, recon=None):
+                 accum_steps=None, ema_decay=None, recon=None, gan_loss="torch"):
         """recon: a `ReconLoss` with `point` and `gdl_alpha` only (the stage-1 loss has no time axis to weight: temporal weights raise
         ValueError); `step` and `eval_step` then also return "AE_L1".
+
+        gan_loss: "torch" or "fused", as in `NARTrainer`: the discriminator update's two losses and 0.5 * lam_gan * (their sum) in one
+        `ops.gan_loss_pair`, the generator's term in one `ops.gan_loss`.
 
         schedule / skip_nonfinite: the device-resident optimizer controls of `FlatAdamW` (optim.py) for both optimizers; `step` then
         also returns "lr_G", "lr_D", "skipped_G", "skipped_D".  The two decisions are independent: a non-finite discriminator gradient
@@ -1311,6 +1349,7 @@ class AETrainer(_ReconMixin):
             raise ValueError("accum_steps > 1 / ema_decay are not available for the stage-1 step: its two optimizers alternate inside "
                              "one iteration and have no accumulation window")
         self._init_recon(recon)
+        self._init_gan_loss(gan_loss, gan_mode)
         if recon is not None and recon.has_weights:
             raise ValueError("AETrainer: temporal weights are not available for the stage-1 loss (ReconLoss point and gdl_alpha only)")
         self.enc, self.dec, self.disc = enc, dec, disc
@@ -1352,12 +1391,16 @@ class AETrainer(_ReconMixin):
                 m.eval()
         x = torch.cat([past, future], dim=1)
         rec = self.dec(self.enc(x))
-        l_fake = self.gan(self.disc(rec.flatten(0, 1)), False)
-        l_real = self.gan(self.disc(x.flatten(0, 1)), True)
-        l_gan = self.gan(self.disc(rec.flatten(0, 1)), True)
+        if self.gan_fused:
+            l_fake, l_real, l_D = self._gan_pair(self.disc(rec.flatten(0, 1)), self.disc(x.flatten(0, 1)))
+        else:
+            l_fake = self.gan(self.disc(rec.flatten(0, 1)), False)
+            l_real = self.gan(self.disc(x.flatten(0, 1)), True)
+            l_D = None
+        l_gan = self._gan_term(self.disc(rec.flatten(0, 1)))
         l_mse, l_gdl, l_point, extra = self._ae_recon(rec, x)
         out = {"AEgan": l_gan, "AE_MSE": l_mse, "AE_GDL": l_gdl, "AE_total": self.lam_gan * l_gan + l_point + l_gdl,
-               "Dtotal": (l_fake + l_real) * 0.5 * self.lam_gan, "Dfake": l_fake, "Dreal": l_real}
+               "Dtotal": (l_fake + l_real) * 0.5 * self.lam_gan if l_D is None else l_D, "Dfake": l_fake, "Dreal": l_real}
         out.update(extra)
         if meters is not None:
             meters.update(out)
@@ -1377,15 +1420,18 @@ class AETrainer(_ReconMixin):
         for p in self.disc.parameters():
             p.requires_grad_(True)
         self.opt_D.zero_grad()
-        l_fake = self.gan(self.disc(rec.detach().flatten(0, 1)), False)
-        l_real = self.gan(self.disc(x.flatten(0, 1)), True)
-        loss_D = (l_fake + l_real) * 0.5 * self.lam_gan
+        if self.gan_fused:
+            l_fake, l_real, loss_D = self._gan_pair(self.disc(rec.detach().flatten(0, 1)), self.disc(x.flatten(0, 1)))
+        else:
+            l_fake = self.gan(self.disc(rec.detach().flatten(0, 1)), False)
+            l_real = self.gan(self.disc(x.flatten(0, 1)), True)
+            loss_D = (l_fake + l_real) * 0.5 * self.lam_gan
         loss_D.backward()
         self.opt_D.step()
         # ---- generator (cal_lossG, :31-42)
         for p in self.disc.parameters():
             p.requires_grad_(False)
-        l_gan = self.gan(self.disc(rec.flatten(0, 1)), True)
+        l_gan = self._gan_term(self.disc(rec.flatten(0, 1)))
         l_mse, l_gdl, l_point, extra = self._ae_recon(rec, x)
         loss_G = self.lam_gan * l_gan + l_point + l_gdl
         loss_G.backward()
