@@ -169,6 +169,11 @@ GAN_SIGNATURES = {
     "vptr_gan_loss_fwd": [P, L, L, I, P, L, L, I, I, F, F, F, P, P, P],
     "vptr_gan_loss_bwd": [P, L, L, I, P, P, L, L, I, P, I, F, F, F, P, P, P, P],
 }
+# parameter groups of the optimizer controls (per-group lr scale and weight decay), declared in include/vptr_hip_groups.h (additive as well)
+GROUP_SIGNATURES = {
+    "vptr_optim_group_scalars": [P, P, P, I, P],
+    "vptr_adamw_groups": [P, P, P, P, P, P, L, P, P, P, I, P],
+}
 
 
 def _load():
@@ -177,7 +182,7 @@ def _load():
             "vptr_amd: %s is missing. Build it with `python -m vptr_amd.build` (needs hipcc, gfx950). "
             "There is no CPU / PyTorch fallback for the VPTR hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(GAN_SIGNATURES.items()):
+    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(GAN_SIGNATURES.items()) + list(GROUP_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.argtypes = argt
         fn.restype = c_int

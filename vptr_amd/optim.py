@@ -26,6 +26,11 @@ S_BETA1, S_BETA2, S_EPS = 11, 12, 13
 # word indices of the third record, `window` (include/vptr_hip_accum.h): words 0 .. 7 are the host's, 8 .. 15 the device's
 W_ACCUM_STEPS, W_EMA_DECAY, W_EMA_WARMUP = range(3)
 W_MICRO, W_APPLY_NOW, W_EMA_OMD, W_EMA_UPDATES = range(8, 12)
+# the group tables (include/vptr_hip_groups.h): ghyper[G][4] = {lr_scale, weight_decay, -, -}, gstate[G][4] = {step_size, decay, lr, -}
+MAX_GROUPS, G_WORDS = 16, 4
+G_LR_SCALE, G_WEIGHT_DECAY = 0, 1
+GS_STEP_SIZE, GS_DECAY, GS_LR = 0, 1, 2
+SCALE_KEY = "vptr_lr_scale"   # the key `FlatAdamW.state_dict` adds to every group of a grouped optimizer
 SKIP_HOLD = 2.0            # state[S_SKIP_NOW] while a window is open (0 apply, 1 skipped)
 WORDS = 16
 MAX_STEPS = 1 << 24        # W and S travel as fp32 words, and the step counter is an fp32 too: whole numbers are exact below 2^24
@@ -281,3 +286,147 @@ class OptimControls:
 
     def adamw(self, p, g, m, v, n):
         check(lib.vptr_adamw_ctl(ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(self.state), stream()), "vptr_adamw_ctl")
+
+
+# ---- parameter groups (include/vptr_hip_groups.h, csrc/param_groups.hip) ------------------------------------------------------------
+def resolve_param_groups(params, param_groups):
+    """`FlatAdamW(param_groups=...)` against the optimizer's parameter list -> (group index of every parameter, [(lr_scale, weight_decay
+    or None)] per group).  Each entry is a dict {"params": [...], "lr_scale": 1.0, "weight_decay": None}; None inherits the optimizer's
+    weight decay.  Parameters no entry lists form group 0 with the defaults (lr_scale 1, inherited decay) and the listed groups follow
+    as 1, 2, ...; when every parameter is listed there is no such group and entry i is group i.  ValueError: a parameter in two groups,
+    a parameter that is not the optimizer's, an unknown key, more than 16 groups, a non-finite or negative value."""
+    if not isinstance(param_groups, (list, tuple)):
+        raise ValueError("param_groups must be a list of dicts, got %r" % type(param_groups).__name__)
+    index = {id(p): i for i, p in enumerate(params)}
+    group_of, specs = [None] * len(params), []
+    for j, grp in enumerate(param_groups):
+        if not isinstance(grp, dict) or "params" not in grp or set(grp) - {"params", "lr_scale", "weight_decay"}:
+            raise ValueError("param_groups[%d] must be a dict with 'params' and optionally 'lr_scale', 'weight_decay', got %r"
+                             % (j, sorted(grp) if isinstance(grp, dict) else grp))
+        scale = _finite("param_groups[%d]['lr_scale']" % j, grp.get("lr_scale", 1.0), 0.0)
+        wd = grp.get("weight_decay")
+        if wd is not None:
+            wd = _finite("param_groups[%d]['weight_decay']" % j, wd, 0.0)
+        for p in grp["params"]:
+            i = index.get(id(p))
+            if i is None:
+                raise ValueError("param_groups[%d] lists a parameter of shape %s that is not one of the optimizer's (trainable) parameters"
+                                 % (j, tuple(getattr(p, "shape", ()))))
+            if group_of[i] is not None:
+                raise ValueError("parameter %d (shape %s) is in param_groups[%d] and param_groups[%d]" % (i, tuple(p.shape), group_of[i], j))
+            group_of[i] = j
+        specs.append((scale, wd))
+    if any(g is None for g in group_of) or not specs:
+        group_of, specs = [0 if g is None else g + 1 for g in group_of], [(1.0, None)] + specs
+    if len(specs) > MAX_GROUPS:
+        raise ValueError("%d parameter groups (the unlisted parameters' group included); at most %d" % (len(specs), MAX_GROUPS))
+    return group_of, specs
+
+
+def group_map(layout, group_of, numel):
+    """the byte map of a slab of `numel` elements: layout[i] = (offset, numel, ...) of parameter i, group_of[i] its group; the elements no
+    parameter owns (the pad at the slab's end) belong to group 0"""
+    gid = torch.zeros(numel, dtype=torch.uint8)
+    for (off, n, *_), g in zip(layout, group_of):
+        gid[off:off + n] = g
+    return gid
+
+
+_NORMS = (torch.nn.LayerNorm, torch.nn.GroupNorm, torch.nn.modules.batchnorm._NormBase)
+
+
+def no_decay_names(module):
+    """names (as `module.named_parameters()` gives them) of the trainable parameters `no_decay_groups` exempts from weight decay"""
+    out = []
+    for mod_name, mod in module.named_modules():
+        for name, p in mod.named_parameters(recurse=False):
+            if p.requires_grad and (isinstance(mod, _NORMS) or name == "bias" or name.endswith("_bias") or name.endswith("bias_table")
+                                    or name.startswith("pos_") or name.endswith("_pos")):
+                out.append(mod_name + "." + name if mod_name else name)
+    return out
+
+
+def no_decay_groups(module, weight_decay=0.0):
+    """The usual AdamW split as a `param_groups` list of one entry: {"params": [...], "weight_decay": weight_decay (0)}; every other
+    trainable parameter stays unlisted, i.e. in group 0 with the optimizer's own weight decay.  The rule, on each module's DIRECT
+    parameters:
+      * every parameter of a normalisation layer (nn.LayerNorm -- the (C, H, W) affines of the conv-FFNs that the slab stores
+        channel-last included --, nn.GroupNorm, the BatchNorm / InstanceNorm family): weight and bias;
+      * every parameter named `bias` (or `*_bias`): nn.Linear, nn.Conv2d, nn.MultiheadAttention's in_proj_bias, ...;
+      * bias and position TABLES: a parameter whose name ends in `bias_table` (the relative-position bias tables of the local
+        attention) or starts with `pos_` / ends in `_pos` (learned absolute position tables).
+    Everything else (weight matrices, convolution kernels, the learned frame queries) is decayed.  A parameter shared by two modules is
+    listed once."""
+    names = set(no_decay_names(module))
+    seen, params = set(), []
+    for name, p in module.named_parameters():
+        if name in names and id(p) not in seen:
+            seen.add(id(p))
+            params.append(p)
+    return [{"params": params, "weight_decay": weight_decay}]
+
+
+class GroupTable:
+    """The group map and the two group tables of one optimizer (include/vptr_hip_groups.h) and the launches on them.  `ghyper` is written
+    by the host only, one fill kernel per changed word, as `OptimControls._put` writes `hyper`; `gstate` by the device only."""
+
+    def __init__(self, device, gid, specs, default_weight_decay):
+        """gid: uint8 CPU tensor, one group index per slab element; specs: [(lr_scale, weight_decay or None)]"""
+        self.ngroups = len(specs)
+        if not 1 <= self.ngroups <= MAX_GROUPS:
+            raise ValueError("optimizer controls: %d parameter groups, must be 1 .. %d" % (self.ngroups, MAX_GROUPS))
+        if gid.dtype != torch.uint8 or int(gid.max()) >= self.ngroups:
+            raise ValueError("optimizer controls: the group map must be uint8 with every entry below %d" % self.ngroups)
+        self.gid = gid.to(device).contiguous()
+        buf = torch.zeros(2 * MAX_GROUPS * G_WORDS, device=device, dtype=torch.float32)
+        self.ghyper, self.gstate = buf[:MAX_GROUPS * G_WORDS], buf[MAX_GROUPS * G_WORDS:]
+        if self.ghyper.data_ptr() % 64 or self.gstate.data_ptr() % 64:
+            raise RuntimeError("optimizer controls: the allocator returned a group table that is not 64-byte aligned")
+        self._host = [None] * (MAX_GROUPS * G_WORDS)
+        self.lr_scale, self.weight_decay = [1.0] * self.ngroups, [None] * self.ngroups     # weight_decay None: inherits the default
+        self._default = _finite("weight_decay", default_weight_decay, 0.0)
+        for g, (scale, wd) in enumerate(specs):
+            self.set(g, scale, wd, inherit=wd is None)
+
+    def _put(self, idx, value):
+        value = _f32(value)
+        if self._host[idx] != value:
+            self.ghyper[idx:idx + 1].fill_(value)
+            self._host[idx] = value
+
+    def _group(self, g):
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 0 <= g < self.ngroups:
+            raise ValueError("optimizer controls: group %r is not one of 0 .. %d" % (g, self.ngroups - 1))
+        return int(g)
+
+    def set(self, g, lr_scale=None, weight_decay=None, inherit=False):
+        """stream-ordered writes of group g's record words (None: leave as it is; inherit: follow the optimizer's weight decay again)"""
+        g = self._group(g)
+        if lr_scale is not None:
+            self.lr_scale[g] = _finite("lr_scale", lr_scale, 0.0)
+            self._put(g * G_WORDS + G_LR_SCALE, self.lr_scale[g])
+        if inherit or weight_decay is not None:
+            self.weight_decay[g] = None if inherit else _finite("weight_decay", weight_decay, 0.0)
+            self._put(g * G_WORDS + G_WEIGHT_DECAY, self.decay_of(g))
+
+    def decay_of(self, g):
+        return self._default if self.weight_decay[g] is None else self.weight_decay[g]
+
+    def set_default_weight_decay(self, weight_decay):
+        """the optimizer's own weight decay changed: the groups that inherit it follow"""
+        self._default = _finite("weight_decay", weight_decay, 0.0)
+        for g in range(self.ngroups):
+            if self.weight_decay[g] is None:
+                self._put(g * G_WORDS + G_WEIGHT_DECAY, self._default)
+
+    def lr(self, g):
+        """0-dim fp32 device view: the rate group g used in the last applied step (0 before the first)"""
+        return self.gstate[self._group(g) * G_WORDS + GS_LR]
+
+    # -- launches ---------------------------------------------------------------------------------------------------------------
+    def scalars(self, state):
+        check(lib.vptr_optim_group_scalars(ptr(state), ptr(self.ghyper), ptr(self.gstate), self.ngroups, stream()), "vptr_optim_group_scalars")
+
+    def adamw(self, p, g, m, v, ema, n, state, window):
+        check(lib.vptr_adamw_groups(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(self.gid), n, ptr(state), ptr(window) if ema is not None else None,
+                                    ptr(self.gstate), self.ngroups, stream()), "vptr_adamw_groups")

@@ -39,7 +39,8 @@ import torch.nn.functional as F
 from . import ops
 from ._lib import check, lib, ptr, stream
 from .model.criterion import GDL, GANLoss, L1Loss, MSELoss, temporal_weight_func
-from .optim import S_GRAD_NORM, S_LR_NOW, S_SKIPPED_IN_A_ROW, S_SKIPPED_TOTAL, STATE_KEY, W_APPLY_NOW, W_MICRO, LRSchedule, OptimControls
+from .optim import (S_GRAD_NORM, S_LR_NOW, S_SKIPPED_IN_A_ROW, S_SKIPPED_TOTAL, SCALE_KEY, STATE_KEY, W_APPLY_NOW, W_MICRO, GroupTable, LRSchedule, OptimControls,
+                    group_map, resolve_param_groups)
 
 
 _HIP_NODE_TYPES = {0: "kernel", 1: "memcpy", 2: "memset", 3: "host", 4: "graph", 5: "empty", 6: "wait_event", 7: "event_record",
@@ -253,19 +254,31 @@ class FlatAdamW:
     leave parameters, moments, step count and schedule position bit for bit as they are.  `applied()` tells which kind a call was.
     With ema_decay an EMA of the parameters (`ema`, laid out like `flat`, seeded with the parameters) is updated inside the update
     kernel: ema += (1 - d_now) (p_new - ema), d_now = min(d, (1 + u) / (10 + u)) after u updates with ema_warmup, else d.  The default
-    accum_steps=None is k = 1 without the window record."""
+    accum_steps=None is k = 1 without the window record.
+
+    param_groups (a list of {"params": [...], "lr_scale": 1.0, "weight_decay": None}): switches the controls on as well and adds the
+    group map and group tables (include/vptr_hip_groups.h, csrc/param_groups.hip): torch.optim.AdamW with several param_groups under one
+    LambdaLR and one clip_grad_norm_ over all parameters.  Group g steps with base_lr * lr_scale_g * schedule factor and its own
+    weight decay (None inherits the optimizer's and follows `set_weight_decay`); the clip norm, betas and eps stay global.  Parameters
+    that no entry lists form group 0 with the defaults, the listed groups follow (optim.resolve_param_groups).  lr_scale 0 leaves a
+    group's parameters bit for bit while its moments still move, as torch does with lr = 0; its gradient still counts in the clip norm.
+    `set_group` rewrites a group between steps or replays, `group_lr(g)` is the rate it last used.  `step` then issues sumsq ->
+    prepare -> group scalars -> grouped update -> plane refresh: one kernel node more than the controlled step."""
 
     ctl = None   # optim.OptimControls when the controls are on
     ema = None   # the EMA slab (ema_decay=)
+    groups = None   # optim.GroupTable (param_groups=)
     _windowed = False
 
     def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, channel_last=(), schedule=None,
-                 skip_nonfinite=False, accum_steps=None, ema_decay=None, ema_warmup=True):
+                 skip_nonfinite=False, accum_steps=None, ema_decay=None, ema_warmup=True, param_groups=None):
         """channel_last: ids of [C, ...] parameters that the kernels consume channel-last (the (C,H,W) LayerNorm affines and
         the depthwise 3x3 weights of MlpDWBN): they are STORED channel-last in the slab and exposed as a permuted view of
         their usual shape, so no per-step transposes of the parameter or its gradient remain (AdamW is elementwise, the
         order inside the slab is irrelevant; state_dict / load_state_dict go through strided copies)."""
         self.params = [p for p in params if p.requires_grad]
+        if param_groups is not None:   # validated before any parameter is rebound to the slab
+            self._group_of, group_specs = resolve_param_groups(self.params, param_groups)
         channel_last = set(channel_last)
         dev = self.params[0].device
         total = sum(p.numel() for p in self.params)
@@ -299,8 +312,10 @@ class FlatAdamW:
         self.step_dev = torch.zeros(1, device=dev, dtype=torch.float32)
         self.sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
         self._windowed = accum_steps is not None or ema_decay is not None
-        if schedule is not None or skip_nonfinite or self._windowed:
+        if schedule is not None or skip_nonfinite or self._windowed or param_groups is not None:
             self.ctl = OptimControls(dev, lr, betas, eps, weight_decay, max_grad_norm, schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup)
+        if param_groups is not None:
+            self.groups = GroupTable(dev, group_map(self._layout, self._group_of, total + pad), group_specs, weight_decay)
         if ema_decay is not None:
             self.ema = self.flat.clone()
         if self._windowed:
@@ -338,6 +353,8 @@ class FlatAdamW:
 
     def set_weight_decay(self, weight_decay):
         self._need_ctl("set_weight_decay").set_weight_decay(weight_decay)
+        if self.groups is not None:
+            self.groups.set_default_weight_decay(weight_decay)
         self.weight_decay = weight_decay
 
     def set_max_grad_norm(self, max_grad_norm):
@@ -364,6 +381,32 @@ class FlatAdamW:
     def skipped_in_a_row(self):
         """... since the last applied step (0-dim fp32 device view): a run that no longer recovers shows here"""
         return self._need_ctl("skipped_in_a_row").word(S_SKIPPED_IN_A_ROW)
+
+    # -- parameter groups ----------------------------------------------------------------------------------------------------------
+    def _need_groups(self, what):
+        if self.groups is None:
+            raise RuntimeError("FlatAdamW.%s needs param_groups=" % what)
+        return self.groups
+
+    def set_group(self, g, lr_scale=None, weight_decay=None):
+        """rewrite group g's rate scale and / or weight decay (None: as it is): stream-ordered writes of its record words, effective from
+        the next step, eager or replayed.  A weight decay given here no longer follows `set_weight_decay`."""
+        self._need_groups("set_group").set(g, lr_scale, weight_decay)
+
+    def group_lr(self, g):
+        """the rate group g used in the last applied step (0-dim fp32 device view, 0 before the first step)"""
+        return self._need_groups("group_lr").lr(g)
+
+    def group_params(self, g):
+        """indices into `params` of group g's parameters, in slab order"""
+        self._need_groups("group_params")._group(g)
+        return [i for i, gi in enumerate(self._group_of) if gi == g]
+
+    def _order(self):
+        """parameter indices in the order torch.optim numbers them: group after group, slab order inside a group"""
+        if self.groups is None:
+            return list(range(len(self.params)))
+        return [i for g in range(self.groups.ngroups) for i in self.group_params(g)]
 
     # -- accumulation window and EMA -------------------------------------------------------------------------------------------
     def _need_window(self, what):
@@ -431,11 +474,11 @@ class FlatAdamW:
         self._not_swapped("state_dict")
         state = {}
         step = self.step_dev.detach().clone().reshape(())
-        for i in range(len(self.params)):
-            state[i] = {"step": step.clone(), "exp_avg": self._logical(self.m, i).contiguous().clone(),
+        for k, i in enumerate(self._order()):   # k: the id torch.optim gives the parameter (== i without groups)
+            state[k] = {"step": step.clone(), "exp_avg": self._logical(self.m, i).contiguous().clone(),
                         "exp_avg_sq": self._logical(self.v, i).contiguous().clone()}
             if self.ema is not None:   # an unknown key of a parameter's state travels through torch.optim.AdamW.load_state_dict as well
-                state[i]["ema"] = self._logical(self.ema, i).contiguous().clone()
+                state[k]["ema"] = self._logical(self.ema, i).contiguous().clone()
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "params": list(range(len(self.params)))}
@@ -447,7 +490,17 @@ class FlatAdamW:
                 micro, ema_updates = self.ctl.window_counters()
                 group[STATE_KEY].update(accum_steps=self.ctl.accum_steps, micro=micro, ema_decay=self.ctl.ema_decay, ema_warmup=self.ctl.ema_warmup,
                                         ema_updates=ema_updates)
-        return {"state": state, "param_groups": [group]}
+        if self.groups is None:
+            return {"state": state, "param_groups": [group]}
+        out, first = [], 0
+        for g in range(self.groups.ngroups):   # one entry per group; group 0 carries the controls
+            cnt = len(self.group_params(g))
+            entry = dict(group if g == 0 else {k: v for k, v in group.items() if k != STATE_KEY})
+            entry.update(lr=self.lr * self.groups.lr_scale[g], weight_decay=self.groups.decay_of(g), params=list(range(first, first + cnt)))
+            entry[SCALE_KEY] = self.groups.lr_scale[g]
+            out.append(entry)
+            first += cnt
+        return {"state": state, "param_groups": out}
 
     def load_state_dict(self, sd):
         self._not_swapped("load_state_dict")
@@ -456,10 +509,30 @@ class FlatAdamW:
         if len(ids) != len(self.params):
             raise ValueError("FlatAdamW.load_state_dict: %d parameters in the checkpoint, %d here" % (len(ids), len(self.params)))
         g0 = groups[0]
-        self.lr, self.betas, self.eps, self.weight_decay = g0["lr"], tuple(g0["betas"]), g0["eps"], g0["weight_decay"]
+        order = list(range(len(self.params)))      # which parameter the k-th saved id belongs to
+        if self.groups is None:
+            if any(g["lr"] != g0["lr"] or g["weight_decay"] != g0["weight_decay"] for g in groups):
+                raise ValueError("FlatAdamW.load_state_dict: the checkpoint's %d param_groups differ in lr or weight_decay; build the optimizer "
+                                 "with the same param_groups=" % len(groups))
+            lr, weight_decay = g0["lr"], g0["weight_decay"]
+        elif len(groups) == 1:
+            # an ungrouped checkpoint: base rate and default decay from it, this optimizer's own grouping, scales and group decays stay
+            lr, weight_decay = g0["lr"], g0["weight_decay"]
+        else:
+            lr, weight_decay, scales, decays = self._read_groups(groups)
+            order = self._order()
+        self.lr, self.betas, self.eps = lr, tuple(g0["betas"]), g0["eps"]
+        if self.ctl is None:
+            self.weight_decay = weight_decay
+        else:
+            self.set_weight_decay(weight_decay)
+        if self.groups is not None and len(groups) > 1:
+            for g, (sc, wd) in enumerate(zip(scales, decays)):
+                self.groups.set(g, sc, wd, inherit=wd is None)
         step = None
         with torch.no_grad():
-            for i, (pid, p) in enumerate(zip(ids, self.params)):
+            for pid, i in zip(ids, order):
+                p = self.params[i]
                 st = sd["state"].get(pid)
                 if st is None:  # parameter never stepped
                     self._logical(self.m, i).zero_()
@@ -488,6 +561,22 @@ class FlatAdamW:
                 self._load_window(sd, ids, saved or {})
         ops.invalidate_weight_planes()   # a checkpoint load usually rewrites the parameters too (possibly through .data)
 
+    def _read_groups(self, groups):
+        """a dict with several param_groups against this optimizer's grouping -> (base lr, default weight decay, scale per group, weight
+        decay per group or None for a group that keeps inheriting).  The scale is the `vptr_lr_scale` key, or lr_g / base without it
+        (a torch.optim.AdamW dict), where base is what makes group 0's rate agree with the scale group 0 has here."""
+        T = self.groups
+        if len(groups) != T.ngroups or any(len(g["params"]) != len(self.group_params(j)) for j, g in enumerate(groups)):
+            raise ValueError("FlatAdamW.load_state_dict: the checkpoint has param_groups of sizes %r, this optimizer %r"
+                             % ([len(g["params"]) for g in groups], [len(self.group_params(j)) for j in range(T.ngroups)]))
+        s0 = groups[0].get(SCALE_KEY, T.lr_scale[0])
+        base = groups[0]["lr"] / s0 if s0 > 0 else self.lr
+        scales = [g[SCALE_KEY] if SCALE_KEY in g else (g["lr"] / base if base > 0 else T.lr_scale[j]) for j, g in enumerate(groups)]
+        inheriting = [j for j in range(T.ngroups) if T.weight_decay[j] is None]
+        default = groups[inheriting[0]]["weight_decay"] if inheriting else self.weight_decay
+        decays = [None if (j in inheriting and g["weight_decay"] == default) else g["weight_decay"] for j, g in enumerate(groups)]
+        return base, default, scales, decays
+
     def _load_window(self, sd, ids, saved):
         """Loading always ends on a window boundary: a partial window's gradients are not part of a checkpoint, so resume is bit-exact
         at window boundaries only.  The EMA comes from the checkpoint; a dict without it (torch.optim.AdamW, an optimizer without
@@ -505,7 +594,8 @@ class FlatAdamW:
             return
         with torch.no_grad():
             if all(sd["state"].get(pid) is not None and "ema" in sd["state"][pid] for pid in ids):
-                for i, pid in enumerate(ids):
+                order = self._order() if (self.groups is not None and len(sd["param_groups"]) > 1) else range(len(ids))
+                for i, pid in zip(order, ids):
                     self._logical(self.ema, i).copy_(sd["state"][pid]["ema"])
                 self.ctl.load_window(saved.get("ema_updates", 0.0))
             else:
@@ -565,13 +655,17 @@ class FlatAdamW:
             else:
                 self.ctl.set_grad_scale(grad_scale)
                 self.ctl.prepare(self.step_dev, self.sumsq)
+            if self.groups is not None:   # lane g: group g's step size and decay from the scalars the prepare launch just left
+                self.groups.scalars(self.ctl.state)
         else:
             self.step_dev.add_(1.0)
         prof = ops.profiling.opt
         if prof is not None:   # bench.py's HBM roofline pass: HIP events on the launch stream around the optimizer's streaming kernels
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record()
-        if self.ema is not None:
+        if self.groups is not None:
+            self.groups.adamw(self.flat, self.grad, self.m, self.v, self.ema, n, self.ctl.state, self.ctl.window)
+        elif self.ema is not None:
             self.ctl.adamw_ema(self.flat, self.grad, self.m, self.v, self.ema, n)
         elif self.ctl is not None:
             self.ctl.adamw(self.flat, self.grad, self.m, self.v, n)
@@ -607,8 +701,14 @@ class NARTrainer(_ReconMixin, _GanMixin):
 
     def __init__(self, enc, dec, transformer, batch_size, lr=1e-4, max_grad_norm=1.0, lam_pc=0.1, process_group=None,
                  bucket_mb=64, dec_weight_grads=True, disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False,
-                 accum_steps=None, ema_decay=None, ema_warmup=True, recon=None, gan_loss="torch"):
-        """recon: a `ReconLoss` -- the frame loss then runs on `ops.recon_losses` (L1, a GDL exponent, temporal weights of length Tf), the
+                 accum_steps=None, ema_decay=None, ema_warmup=True, recon=None, gan_loss="torch", param_groups=None):
+        """param_groups: the parameter groups of the transformer's `FlatAdamW` (per-group lr_scale and weight_decay): a list of
+        {"params": [...], "lr_scale": 1.0, "weight_decay": None}, or a callable that takes the transformer and returns one, e.g.
+        `optim.no_decay_groups`.  It switches the device-resident controls on; `trainer.opt.set_group(g, ...)` between steps or replays
+        changes the next update, `trainer.opt.group_lr(g)` can go into `DeviceLossMeters`.  The discriminator's optimizer (`disc=`) stays
+        ungrouped.
+
+        recon: a `ReconLoss` -- the frame loss then runs on `ops.recon_losses` (L1, a GDL exponent, temporal weights of length Tf), the
         returned terms gain "T_L1", and `set_temporal_weight` rewrites the weights between steps or replays.  None: `ops.mse_gdl` as ever.
 
         gan_loss: "torch" (the `GANLoss` module: ATen expand, BCE, mean and their autograd) or "fused" (`ops.gan_loss_pair` for the
@@ -628,7 +728,7 @@ class NARTrainer(_ReconMixin, _GanMixin):
         skipped step leaves parameters, moments and step count untouched; it still refreshes the weight planes (from unchanged weights),
         still advances the dropout seed, and BatchNorm running statistics of the forward pass it belongs to have been updated already."""
         self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup, gan_loss)
+                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup, gan_loss, param_groups)
         self._init_recon(recon)
         # loss_name_list MSE / GDL(alpha=1) / BiPatchNCE(N, Tf, 8, 8, temperature 1.0) of train_NAR.py:176-179 run as the fused kernels of
         # csrc/losses.hip (ops.mse_gdl, ops.nce_loss): plain kernel launches only, so the step can live in a hipGraph (DESIGN.md section 6)
@@ -639,7 +739,7 @@ class NARTrainer(_ReconMixin, _GanMixin):
             self._bufsync = BufferSync(self.T, 0, process_group)   # DDP's per-forward broadcast of rank 0's BatchNorm statistics
 
     def _init_stage2(self, enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                     schedule, skip_nonfinite, accum_steps=None, ema_decay=None, ema_warmup=True, gan_loss="torch"):
+                     schedule, skip_nonfinite, accum_steps=None, ema_decay=None, ema_warmup=True, gan_loss="torch", param_groups=None):
         """what both stage-2 recipes construct: frozen auto-encoder, optional adversarial branch, the transformer's flat-slab optimizer"""
         if disc is not None and (ema_decay is not None or (accum_steps is not None and accum_steps != 1)):
             raise ValueError("accum_steps > 1 / ema_decay are not available with the adversarial branch (disc=): the discriminator's "
@@ -661,7 +761,8 @@ class NARTrainer(_ReconMixin, _GanMixin):
             mod._vptr_frozen = True  # never stepped here: packed conv weights / eval-BN folds are cached (ops.frozen_weights)
         self.opt = FlatAdamW(self.T.parameters(), lr=lr, max_grad_norm=max_grad_norm, channel_last=_channel_last_ids(self.T),
                              schedule=schedule, skip_nonfinite=skip_nonfinite, accum_steps=accum_steps,
-                             ema_decay=ema_decay, ema_warmup=ema_warmup)
+                             ema_decay=ema_decay, ema_warmup=ema_warmup,
+                             param_groups=param_groups(self.T) if callable(param_groups) else param_groups)
         self._bufsync = None
         self._graph = None
 
@@ -1296,12 +1397,12 @@ class FARTrainer(NARTrainer):
 
     def __init__(self, enc, dec, transformer, lr=1e-4, max_grad_norm=1.0, process_group=None, bucket_mb=64, dec_weight_grads=True,
                  disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False, accum_steps=None, ema_decay=None,
-                 ema_warmup=True, recon=None, gan_loss="torch"):
-        """schedule / skip_nonfinite / accum_steps / ema_decay / ema_warmup / recon / gan_loss: as in `NARTrainer`; the temporal weights of a
-        `ReconLoss` have Tp - 1 + Tf entries here, one per frame of cat(past[:, 1:], future)"""
+                 ema_warmup=True, recon=None, gan_loss="torch", param_groups=None):
+        """schedule / skip_nonfinite / accum_steps / ema_decay / ema_warmup / recon / gan_loss / param_groups: as in `NARTrainer`; the temporal
+        weights of a `ReconLoss` have Tp - 1 + Tf entries here, one per frame of cat(past[:, 1:], future)"""
         # no BufferSync: the FAR transformer has no BatchNorm (LayerNorm conv-FFNs), nothing to broadcast per forward
         self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup, gan_loss)
+                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup, gan_loss, param_groups)
         self._init_recon(recon)
 
     def _encode(self, past, future):
@@ -1333,9 +1434,11 @@ class AETrainer(_ReconMixin, _GanMixin):
     AdamW with weight_decay 0, so both optimizers are `FlatAdamW` slabs (no clipping in this stage)."""
 
     def __init__(self, enc, dec, disc, lr=2e-4, lam_gan=0.01, betas=(0.5, 0.999), gan_mode="vanilla", schedule=None, skip_nonfinite=False,
-                 accum_steps=None, ema_decay=None, recon=None, gan_loss="torch"):
+                 accum_steps=None, ema_decay=None, recon=None, gan_loss="torch", param_groups=None):
         """recon: a `ReconLoss` with `point` and `gdl_alpha` only (the stage-1 loss has no time axis to weight: temporal weights raise
         ValueError); `step` and `eval_step` then also return "AE_L1".
+
+        param_groups: not available here (ValueError): stage 1 is plain Adam without weight decay on both optimizers.
 
         gan_loss: "torch" or "fused", as in `NARTrainer`: the discriminator update's two losses and 0.5 * lam_gan * (their sum) in one
         `ops.gan_loss_pair`, the generator's term in one `ops.gan_loss`.
@@ -1348,6 +1451,9 @@ class AETrainer(_ReconMixin, _GanMixin):
         if ema_decay is not None or (accum_steps is not None and accum_steps != 1):
             raise ValueError("accum_steps > 1 / ema_decay are not available for the stage-1 step: its two optimizers alternate inside "
                              "one iteration and have no accumulation window")
+        if param_groups is not None:
+            raise ValueError("param_groups are not available for the stage-1 step (Adam without weight decay on Enc + Dec and on the "
+                             "discriminator); they belong to the stage-2 trainers' transformer optimizer")
         self._init_recon(recon)
         self._init_gan_loss(gan_loss, gan_mode)
         if recon is not None and recon.has_weights:
