@@ -1,5 +1,5 @@
 /*
- * vptr_hip_accum.h -- gradient accumulation and EMA weights of the device-resident optimizer controls (csrc/accum.hip).  Additive to
+ * vptr_hip_accum.h -- gradient accumulation and EMA weights of the device-resident optimizer controls (csrc/optim.hip).  Additive to
  * ABI 10 of vptr_hip.h, to vptr_hip_ext.h, vptr_hip_optim.h and vptr_hip_convffn.h; same conventions (borrow-only, stream-ordered, 0 on
  * success, the thread-local error message, NOTHING launched and nothing written on a rejected call); the ABI version and the export table
  * are unchanged, a library that lacks one of these symbols fails when vptr_amd._lib binds it (ACCUM_SIGNATURES).

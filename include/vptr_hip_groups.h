@@ -1,5 +1,5 @@
 /*
- * vptr_hip_groups.h -- parameter groups of the device-resident optimizer controls (csrc/param_groups.hip): a learning-rate scale and a
+ * vptr_hip_groups.h -- parameter groups of the device-resident optimizer controls (csrc/optim.hip): a learning-rate scale and a
  * weight decay per group of slab elements.  Additive to ABI 10 of vptr_hip.h and to vptr_hip_ext.h, vptr_hip_optim.h, vptr_hip_convffn.h,
  * vptr_hip_accum.h, vptr_hip_loss.h and vptr_hip_gan.h; same conventions (borrow-only, stream-ordered, 0 on success, the thread-local
  * error message, NOTHING launched and nothing written on a rejected call); the ABI version and the export table are unchanged, a library
@@ -39,7 +39,7 @@ extern "C" {
  *   step_size_g = state[STEP_SIZE] * lr_scale_g       (state holds lr_now / (1 - beta1^step) but not the bias correction itself, so the
  *                                                      scale multiplies the quotient: one rounding more than fp32(lr_g / bc1), none at
  *                                                      lr_scale 1 or 0)
- *   decay_g     = fmaf(-lr_g, weight_decay_g, 1)      (the expression of csrc/optim_prepare.h)
+ *   decay_g     = fmaf(-lr_g, weight_decay_g, 1)      (adamw_scalars' expression, csrc/optim.hip)
  * With lr_scale_g = 1 and weight_decay_g = hyper[WEIGHT_DECAY], step_size_g and decay_g are bit-identical to state[STEP_SIZE] and
  * state[DECAY].  With lr_scale_g = 0: step_size_g = 0, decay_g = 1.
  * Rejected: a NULL pointer, ngroups outside 1 .. 16, state, ghyper or gstate not 64-byte aligned.  The VALUES of ghyper are device

@@ -694,7 +694,7 @@ def droppath_emu(keep, maxcount, seed, site0):
 
 
 def step_tail_class(op, **g):
-    """the launch class of a call of the step's tail, restated from the launchers (csrc/losses.hip, csrc/elementwise.hip):
+    """the launch class of a call of the step's tail, restated from the launchers (csrc/losses.hip, csrc/optim.hip):
     "mse_gdl" (planes, H, W): bands of 16 rows, partials = workgroups of the forward, rows of the last band, trips of a workgroup's element loop
         and of the final kernel's loop over the partials, workgroups of the backward, scratch floats;
     "nce" (frames, L, C): NV instantiation of the backward (or "reject"), its dynamic LDS bytes and grid, 64-row blocks, dead rows of the last

@@ -83,7 +83,7 @@ def _ulps(got, want):
 
 # --------------------------------------------------------------------------------------------------- the expected record, from the header's text
 def update_scalars_f32(lr, step, b1, b2, eps, wd, sumsq, max_norm, grad_scale):
-    """adamw_kernel's launch-uniform expressions in numpy fp32 (elementwise.hip); max_norm <= 0: no clipping"""
+    """adamw_kernel's launch-uniform expressions in numpy fp32 (optim.hip); max_norm <= 0: no clipping"""
     lr, k, b1, b2, eps, wd = (F(x) for x in (lr, step, b1, b2, eps, wd))
     coef = clip_coef_f32(sumsq if max_norm > 0 else None, max_norm, grad_scale)
     bc1, bc2 = -np.expm1(k * np.log1p(b1 - F(1))), -np.expm1(k * np.log1p(b2 - F(1)))

@@ -2,7 +2,7 @@
 more partials than one trip of the final kernel, one-row last bands, the minimum plane, W above the workgroup, either upstream scalar NULL,
 exact ties; vptr_nce_fwd / _bwd in every NV class of the backward and on both sides of every class boundary, dead rows with partial token
 chunks, channel widths that are no multiple of 16, both temperatures, gout present and NULL, the scratch's score / log-sum-exp sections, the
-documented rejects), the optimizer of csrc/elementwise.hip (vptr_sumsq with its unrolled loop, unaligned branch and accumulate contract,
+documented rejects), the optimizer of csrc/optim.hip (vptr_sumsq with its unrolled loop, unaligned branch and accumulate contract,
 vptr_sumsq_ws, vptr_adamw in every launch class, with the clip active / inactive / absent, grad_scale, and the applied update at full fp32
 resolution per step count), and the counter-based RNG of csrc/common.h bit for bit (vptr_dropout, vptr_droppath_scales).
 

@@ -1,4 +1,4 @@
-"""Gradient accumulation and EMA weights of the device-resident optimizer controls (csrc/accum.hip) through the C ABI
+"""Gradient accumulation and EMA weights of the device-resident optimizer controls (csrc/optim.hip) through the C ABI
 (include/vptr_hip_accum.h): vptr_accum_begin (zero-fill at a window start, the partial sum left alone otherwise, every launch class),
 vptr_optim_prepare_accum (bit identity with vptr_optim_prepare at k = 1, the window sequences at k = 3, non-finite sums on a hold and on a
 close, k lowered inside a window, the EMA coefficient against its fp64 mirror), vptr_adamw_ctl_ema (p / m / v bit-identical to

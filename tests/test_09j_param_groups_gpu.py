@@ -1,4 +1,4 @@
-"""Parameter groups of the device-resident optimizer controls (csrc/param_groups.hip) through the C ABI (include/vptr_hip_groups.h):
+"""Parameter groups of the device-resident optimizer controls (csrc/optim.hip) through the C ABI (include/vptr_hip_groups.h):
 vptr_optim_group_scalars (the per-group rate, step size and decay against their definitions, bit identity with the state record at
 lr_scale 1, skip and hold) and vptr_adamw_groups in both forms (every size and launch class, each pointer off its grid, group boundaries
 inside a float4 / at a multiple of 1024 / at the last element, an empty group, 1 / 2 / 16 groups, a map byte out of range, bit identity

@@ -35,7 +35,7 @@ def test_group_signatures_match_header_and_library():
     assert all(not NAMES & o for o in others)
     assert len(_lib.EXPORTS) == 77 and _lib.lib.vptr_abi_version() == 10
     from vptr_amd.build import SOURCES
-    assert "param_groups.hip" in SOURCES
+    assert "optim.hip" in SOURCES
     # the table layout: header, host layer and the cases agree
     defs = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define VPTR_GRP_(\w+) (\d+)", text)}
     assert defs["MAX"] == optim.MAX_GROUPS == G.MAX_GROUPS == 16 and defs["WORDS"] == optim.G_WORDS == G.G_WORDS == 4

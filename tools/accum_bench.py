@@ -1,4 +1,4 @@
-"""Measurements of gradient accumulation and EMA weights (csrc/accum.hip) -> profiles/accum_ema.md.
+"""Measurements of gradient accumulation and EMA weights (csrc/optim.hip) -> profiles/accum_ema.md.
 
     python tools/accum_bench.py [--reps 20] [--out profiles/accum_ema.md]
 
@@ -100,8 +100,8 @@ def main():
     v.abs_()
     g = torch.randn(n, device=dev) * 1e-3
     step_dev, sumsq = torch.zeros(1, device=dev), (g.double() ** 2).sum().float().reshape(1)
-    ctl.prepare_accum(step_dev, sumsq)
-    res = alternate([("vptr_adamw_ctl (7 streams)", lambda: ctl.adamw(p, g, m, v, n)), ("vptr_adamw_ctl_ema (9 streams)", lambda: ctl.adamw_ema(p, g, m, v, e, n))], args.reps)
+    ctl.prepare(step_dev, sumsq)
+    res = alternate([("vptr_adamw_ctl (7 streams)", lambda: ctl.update(p, g, m, v, n)), ("vptr_adamw_ctl_ema (9 streams)", lambda: ctl.update(p, g, m, v, n, ema=e))], args.reps)
     a, b = statistics.median(res["vptr_adamw_ctl (7 streams)"]), statistics.median(res["vptr_adamw_ctl_ema (9 streams)"])
     lines += ["## 2. vptr_adamw_ctl_ema against vptr_adamw_ctl (%d floats)" % n, "", "| kernel | median | min | max | spread | TB/s moved |", "|---|---|---|---|---|---|",
               row("vptr_adamw_ctl (7 streams)", res["vptr_adamw_ctl (7 streams)"], 7 * 4 * n), row("vptr_adamw_ctl_ema (9 streams)", res["vptr_adamw_ctl_ema (9 streams)"], 9 * 4 * n), "",

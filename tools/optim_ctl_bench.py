@@ -48,11 +48,11 @@ def kernels(dev, repeats):
 
     def controlled():
         ctl.prepare(step_b, sumsq)
-        ctl.adamw(p, g, m, v, n)
+        ctl.update(p, g, m, v, n)
 
     def skipped():
         ctl_skip.prepare(step_c, nan)
-        ctl_skip.adamw(p, g, m, v, n)
+        ctl_skip.update(p, g, m, v, n)
 
     rows = {"adamw_us": [], "prepare_adamw_ctl_us": [], "skipped_us": []}
     fns = (("adamw_us", plain), ("prepare_adamw_ctl_us", controlled), ("skipped_us", skipped))

@@ -1,4 +1,4 @@
-"""Measurements of the parameter groups of the optimizer controls (csrc/param_groups.hip) -> the timing section of profiles/param_groups.md.
+"""Measurements of the parameter groups of the optimizer controls (csrc/optim.hip) -> the timing section of profiles/param_groups.md.
 
     python tools/param_groups_bench.py [--reps 20] [--out FILE] [--skip-step]
 
@@ -34,7 +34,7 @@ def kernels(n, dev, reps, lines):
     v.abs_()
     g = torch.randn(n, device=dev) * 1e-3
     step_dev, sumsq = torch.zeros(1, device=dev), (g.double() ** 2).sum().float().reshape(1)
-    ctl.prepare_accum(step_dev, sumsq)
+    ctl.prepare(step_dev, sumsq)
     tabs = {}
     for ng in (1, 2, 16):
         # contiguous runs of unequal length, as parameters lie in a slab; boundaries fall inside float4s
@@ -44,9 +44,9 @@ def kernels(n, dev, reps, lines):
         tabs[ng] = GroupTable(dev, gid, [(1.0 if j % 2 == 0 else 0.5, None if j % 3 else 0.0) for j in range(ng)], 1e-2)
         tabs[ng].scalars(ctl.state)
     for ema, ref_name, streams in ((None, "vptr_adamw_ctl", 7), (e, "vptr_adamw_ctl_ema", 9)):
-        ref = (lambda: ctl.adamw(p, g, m, v, n)) if ema is None else (lambda: ctl.adamw_ema(p, g, m, v, e, n))
+        ref = lambda: ctl.update(p, g, m, v, n, ema=ema)
         variants = [(ref_name, ref)] + [("vptr_adamw_groups, %d group%s" % (ng, "" if ng == 1 else "s"),
-                                         (lambda t: lambda: t.adamw(p, g, m, v, ema, n, ctl.state, ctl.window))(tabs[ng])) for ng in (1, 2, 16)]
+                                         (lambda t: lambda: ctl.update(p, g, m, v, n, ema=ema, groups=t))(tabs[ng])) for ng in (1, 2, 16)]
         res = alternate(variants, reps)
         base = statistics.median(res[ref_name])
         spread = (max(res[ref_name]) - min(res[ref_name])) / base

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libvptr_hip.so")
-SOURCES = ["api.hip", "gemm.hip", "gemm_p16.hip", "layernorm.hip", "norm_act.hip", "dwconv.hip", "attn.hip", "attn_mfma.hip", "attn16.hip", "elementwise.hip", "conv7.hip", "losses.hip", "recon_loss.hip", "gan_loss.hip", "metrics.hip", "meters.hip", "optim.hip", "accum.hip", "param_groups.hip", "ingest.hip", "panels.hip", "winograd.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_p16.hip", "layernorm.hip", "norm_act.hip", "dwconv.hip", "attn.hip", "attn_mfma.hip", "attn16.hip", "elementwise.hip", "conv7.hip", "losses.hip", "recon_loss.hip", "gan_loss.hip", "metrics.hip", "meters.hip", "optim.hip", "ingest.hip", "panels.hip", "winograd.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-ffp-contract=fast", "-fno-slp-vectorize",
          "-Wno-unused-result"]
 
@@ -40,7 +40,7 @@ def _digest(paths):
 def _compile(src, force):
     obj = os.path.join(OBJ, src.replace(".hip", ".o"))
     stamp = obj + ".sha"
-    deps = [os.path.join(CSRC, src), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_shared.h"), os.path.join(CSRC, "attn_mfma.h"), os.path.join(CSRC, "optim_prepare.h"),
+    deps = [os.path.join(CSRC, src), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_shared.h"), os.path.join(CSRC, "attn_mfma.h"),
             os.path.join(CSRC, "attn_route.h"), os.path.join(HERE, "..", "include", "vptr_hip.h"), os.path.join(HERE, "..", "include", "vptr_hip_ext.h"),
             os.path.join(HERE, "..", "include", "vptr_hip_optim.h"), os.path.join(HERE, "..", "include", "vptr_hip_convffn.h"),
             os.path.join(HERE, "..", "include", "vptr_hip_accum.h"), os.path.join(HERE, "..", "include", "vptr_hip_loss.h"),

@@ -1,5 +1,5 @@
 // Layout and elementwise helpers (gfx950): NCHW <-> token-major transposes through LDS, activation backward,
-// standalone dropout, row scaling, folded-BN/ReLU backward, and the clip + AdamW optimizer step.  All HBM-bound.
+// standalone dropout, row scaling, and folded-BN/ReLU backward.  All HBM-bound.
 #include "common.h"
 
 // [B, R, S] -> [B, S, R] tiled transpose, 32x32 tiles via LDS (+1 pad), 256 threads.
@@ -214,132 +214,6 @@ extern "C" int vptr_bnrelu_bwd(const float* dy, const float* y, const float* sca
   const int64_t total = rows * C;
   const int blocks = (int)hmin64((total + 255) / 256, 8192);
   bnrelu_bwd_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(dy, y, scale, dx, rows, C);
-  VPTR_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---- optimizer -------------------------------------------------------------------------------------------------
-// 1024-thread workgroups, at most 256 of them: the kernel ends in one fp32 atomic per workgroup onto a total whose ulp is 1e-7 of it, so the
-// error is a random walk of sqrt(workgroups) roundings -- 2.5e-7 rms with 256, 7e-7 with 2048
-__global__ __launch_bounds__(1024) void sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ out) {
-  __shared__ float red[16];
-  float s = 0.f;
-  if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {   // 16-byte loads, four of them in flight per thread
-    const float4* g4 = reinterpret_cast<const float4*>(g);
-    const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * 1024;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-    for (; i + 3 * stride < n4; i += 4 * stride) {
-      const float4 v0 = g4[i], v1 = g4[i + stride], v2 = g4[i + 2 * stride], v3 = g4[i + 3 * stride];
-      a0 += (v0.x * v0.x + v0.y * v0.y) + (v0.z * v0.z + v0.w * v0.w);
-      a1 += (v1.x * v1.x + v1.y * v1.y) + (v1.z * v1.z + v1.w * v1.w);
-      a2 += (v2.x * v2.x + v2.y * v2.y) + (v2.z * v2.z + v2.w * v2.w);
-      a3 += (v3.x * v3.x + v3.y * v3.y) + (v3.z * v3.z + v3.w * v3.w);
-    }
-    for (; i < n4; i += stride) {
-      const float4 v0 = g4[i];
-      a0 += (v0.x * v0.x + v0.y * v0.y) + (v0.z * v0.z + v0.w * v0.w);
-    }
-    s = (a0 + a1) + (a2 + a3);
-    for (int64_t t = (n4 << 2) + (int64_t)blockIdx.x * 1024 + threadIdx.x; t < n; t += stride) s += g[t] * g[t];
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 1024) s += g[i] * g[i];
-  }
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) unsafeAtomicAdd(out, s);
-}
-extern "C" int vptr_sumsq(const float* g, int64_t n, float* sumsq_dev, vptr_stream_t stream) {
-  VPTR_CHECK(n > 0 && sumsq_dev, "sumsq: bad arguments");
-  const int blocks = (int)hmin64((n + 1023) / 1024, 256);
-  sumsq_kernel<<<blocks, 1024, 0, (hipStream_t)stream>>>(g, n, sumsq_dev);
-  VPTR_LAUNCH_CHECK();
-  return 0;
-}
-
-// Fixed-order variant: every block leaves its partial in a caller-owned workspace, one block adds the partials in index order
-// (run-to-run reproducible: no atomics; vptr_set_deterministic mode of FlatAdamW)
-__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ ws) {
-  __shared__ float red[16];
-  // compensated (Kahan) per-thread sum: with few workgroups a thread adds tens of thousands of squares, and the many squares below half an
-  // ulp of a plain running sum are lost one-sidedly (4.6e-6 low with one workgroup on 10.5 M elements)
-  float s = 0.f, c = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float y = fmaf(g[i], g[i], -c), t = s + y;
-    c = (t - s) - y;
-    s = t;
-  }
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) ws[blockIdx.x] = s;
-}
-__global__ __launch_bounds__(256) void sumsq_final_kernel(const float* __restrict__ ws, int nws, float* __restrict__ out) {
-  __shared__ float red[16];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nws; i += 256) s += ws[i];
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) *out = s;
-}
-extern "C" int vptr_sumsq_ws(const float* g, int64_t n, float* sumsq_dev, float* ws, int nws, vptr_stream_t stream) {
-  VPTR_CHECK(n > 0 && sumsq_dev && ws && nws >= 1 && nws <= 65536, "sumsq_ws: bad arguments");
-  sumsq_partial_kernel<<<nws, 256, 0, (hipStream_t)stream>>>(g, n, ws);
-  sumsq_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(ws, nws, sumsq_dev);
-  VPTR_LAUNCH_CHECK();
-  return 0;
-}
-
-// torch.optim.AdamW semantics (decoupled weight decay, bias correction), clip_grad_norm_ coefficient folded in.
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
-                                                    float wd, const float* __restrict__ step_dev,
-                                                    const float* __restrict__ sumsq_dev, float max_norm, float grad_scale) {
-  const float step = *step_dev;
-  float coef = grad_scale;
-  if (sumsq_dev) {
-    const float total = sqrtf(*sumsq_dev) * grad_scale;
-    coef *= fminf(1.f, max_norm / (total + 1e-6f));
-  }
-  // 1 - b^step without the subtraction: 1.f - powf(0.999f, 2.f) keeps 9 of its 24 bits (the power is rounded next to 1), 3e-6 on the applied
-  // update at steps 2 - 5 where a correct fp32 evaluation stays near 1e-7; b - 1 is exact for b in [0.5, 1].  A few dozen launch-uniform
-  // instructions per thread in front of an HBM-bound loop.
-  const float bc1 = -expm1f(step * log1pf(b1 - 1.f)), bc2 = -expm1f(step * log1pf(b2 - 1.f));
-  const float step_size = lr / bc1;
-  const float inv_sqrt_bc2 = rsqrtf(bc2);
-  // every sum is an explicit FMA: under -ffp-contract=fast the compiler chooses which product of b * m + (1 - b) * g to fuse, and may choose
-  // differently in the two loops below, which must agree bit for bit
-  const float decay = fmaf(-lr, wd, 1.f), ob1 = 1.f - b1, ob2 = 1.f - b2;
-  auto upd = [&](const float graw, float& pi, float& mi, float& vi) {
-    const float gi = graw * coef;
-    mi = fmaf(b1, mi, ob1 * gi);
-    vi = fmaf(b2, vi, (ob2 * gi) * gi);
-    const float denom = fmaf(sqrtf(vi), inv_sqrt_bc2, eps);
-    pi = fmaf(pi, decay, -(step_size * mi / denom));
-  };
-  // 16-byte accesses (round 6: the scalar form issued seven 4-byte memory instructions per element -- 4.8 TB/s on a 3.3 GB stream); same arithmetic
-  // per element, so results are bit-identical.  n4 = 0 when a pointer is not 16-byte aligned.
-  const int64_t n4 = (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0) ? n / 4 : 0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    const float4 g4 = reinterpret_cast<const float4*>(g)[i];
-    float4 p4 = reinterpret_cast<float4*>(p)[i], m4 = reinterpret_cast<float4*>(m)[i], v4 = reinterpret_cast<float4*>(v)[i];
-    upd(g4.x, p4.x, m4.x, v4.x);
-    upd(g4.y, p4.y, m4.y, v4.y);
-    upd(g4.z, p4.z, m4.z, v4.z);
-    upd(g4.w, p4.w, m4.w, v4.w);
-    reinterpret_cast<float4*>(p)[i] = p4;
-    reinterpret_cast<float4*>(m)[i] = m4;
-    reinterpret_cast<float4*>(v)[i] = v4;
-  }
-  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    upd(g[i], pi, mi, vi);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-extern "C" int vptr_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                          float weight_decay, const float* step_dev, const float* sumsq_dev, float max_norm, float grad_scale,
-                          vptr_stream_t stream) {
-  VPTR_CHECK(n > 0 && p && g && m && v && step_dev, "adamw: bad arguments");
-  const int blocks = (int)hmin64((n / 4 + 255) / 256 + 1, 4096);
-  adamw_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step_dev, sumsq_dev,
-                                                       max_norm, grad_scale);
   VPTR_LAUNCH_CHECK();
   return 0;
 }

@@ -1,5 +1,5 @@
 """Device-resident optimizer controls: learning-rate schedules and the non-finite skip of `train.FlatAdamW` (csrc/optim.hip,
-include/vptr_hip_optim.h).
+include/vptr_hip_optim.h), its accumulation window and EMA (include/vptr_hip_accum.h) and its parameter groups (include/vptr_hip_groups.h).
 
 `vptr_adamw` takes its hyper-parameters by value, so a captured step (`NARTrainer.capture`) freezes them into the graph.  With controls the
 hyper-parameters live in a 64-byte device record (`hyper`); `vptr_optim_prepare` -- one single-lane launch behind the gradient's sum of
@@ -112,17 +112,34 @@ def _finite(name, x, lo=None, lo_open=False, hi=None, hi_open=False):
     return float(x)
 
 
+class Record:
+    """A device record the host writes: the device view `dev`, the host's mirror of what it last wrote into each word, and `put` -- one
+    fill kernel per CHANGED word (stream-ordered, no memset node, no host buffer whose lifetime a graph would have to care about).  The
+    kernels need the record 64-byte aligned; a device-written record that follows it in the same buffer at a multiple of 64 bytes is
+    aligned with it."""
+
+    def __init__(self, dev, what="record"):
+        if dev.data_ptr() % 64:
+            raise RuntimeError("optimizer controls: the allocator returned a %s that is not 64-byte aligned" % what)
+        self.dev, self.host = dev, [None] * dev.numel()
+
+    def put(self, idx, value):
+        value = _f32(value)
+        if self.host[idx] != value:
+            self.dev[idx:idx + 1].fill_(value)
+            self.host[idx] = value
+
+
 class OptimControls:
-    """The device records of one optimizer and the launches on them.  `hyper` is written by the host only, one fill kernel per changed
-    word (stream-ordered, no memset node, no host buffer whose lifetime a graph would have to care about); `state` is written by the device
-    only, apart from the zeroing here and `load_counters`.
+    """The device records of one optimizer and the launches on them.  `hyper` is written by the host only (a `Record`); `state` is
+    written by the device only, apart from the zeroing here and `load_counters`.
 
     accum_steps / ema_decay (either one not None) add the third record, `window` (include/vptr_hip_accum.h): gradient accumulation over
-    `accum_steps` micro-steps and the EMA of the parameters.  Its words 0 .. 7 are the host's (the same one-fill-per-changed-word writes),
+    `accum_steps` micro-steps and the EMA of the parameters.  Its words 0 .. 7 are the host's (written through a `Record` as well),
     words 8 .. 15 the device's, apart from the zeroing here, `reset_window` and `load_window`.  `micro_host` mirrors the window position:
     it is deterministic, because neither a hold nor a skipped close moves a window boundary."""
 
-    window = None      # the third record; None: no accumulation window, `prepare` / `adamw` are the launches
+    window = None      # the third record; None: no accumulation window
     micro_host = 0
 
     def __init__(self, device, lr, betas, eps, weight_decay, max_grad_norm, schedule=None, skip_nonfinite=False, accum_steps=None, ema_decay=None,
@@ -132,26 +149,18 @@ class OptimControls:
         windowed = accum_steps is not None or ema_decay is not None
         buf = torch.zeros((3 if windowed else 2) * WORDS, device=device, dtype=torch.float32)
         self.hyper, self.state = buf[:WORDS], buf[WORDS:2 * WORDS]
-        if self.hyper.data_ptr() % 64 or self.state.data_ptr() % 64:
-            raise RuntimeError("optimizer controls: the allocator returned a record that is not 64-byte aligned")
+        self._put = Record(self.hyper).put
         self.schedule = schedule if schedule is not None else LRSchedule()
         self.skip_nonfinite = bool(skip_nonfinite)
-        self._host = [None] * WORDS      # what the host last wrote into each word
         self.write(lr, betas, eps, weight_decay, max_grad_norm, 1.0)
         if windowed:
             self.window = buf[2 * WORDS:]
-            self._whost = [None] * WORDS
+            self._wput = Record(self.window).put
             self.accum_steps, self.ema_decay, self.ema_warmup = 1, None, True
             self.set_accum_steps(1 if accum_steps is None else accum_steps)
             self.set_ema_decay(ema_decay, ema_warmup)
 
     # -- hyper ------------------------------------------------------------------------------------------------------------------
-    def _put(self, idx, value):
-        value = _f32(value)
-        if self._host[idx] != value:
-            self.hyper[idx:idx + 1].fill_(value)
-            self._host[idx] = value
-
     def write(self, lr, betas, eps, weight_decay, max_grad_norm, grad_scale):
         """validate and write every word"""
         self.set_lr(lr)
@@ -205,12 +214,6 @@ class OptimControls:
         if self.window is None:
             raise RuntimeError("optimizer controls: %s needs the accumulation window (accum_steps= or ema_decay=)" % what)
 
-    def _wput(self, idx, value):
-        value = _f32(value)
-        if self._whost[idx] != value:
-            self.window[idx:idx + 1].fill_(value)
-            self._whost[idx] = value
-
     def set_accum_steps(self, k):
         """micro-steps per window; only between windows (the host's mirror of the window position must be 0: see `reset_window`)"""
         self._need_window("set_accum_steps")
@@ -243,7 +246,7 @@ class OptimControls:
         self.micro_host = 0
 
     def advance_mirror(self):
-        """one micro-step passed (called for every `prepare_accum` that is executed: eager here, per replay by the owner of a graph);
+        """one micro-step passed (called for every windowed `prepare` that is executed: eager here, per replay by the owner of a graph);
         -> whether that micro-step closed its window"""
         self.micro_host = (self.micro_host + 1) if self.micro_host + 1 < self.accum_steps else 0
         return self.micro_host == 0
@@ -272,23 +275,28 @@ class OptimControls:
         """zero the gradient slab if a window starts, else leave the partial sum (one kernel node)"""
         check(lib.vptr_accum_begin(ptr(grad), grad.numel(), ptr(self.window), stream()), "vptr_accum_begin")
 
-    def prepare_accum(self, step_dev, sumsq_dev):
+    def prepare(self, step_dev, sumsq_dev):
+        """the single-lane launch behind the sum of squares; with a window its accumulating form, which also moves the host's mirror"""
+        if self.window is None:
+            check(lib.vptr_optim_prepare(ptr(self.hyper), ptr(self.state), ptr(step_dev), ptr(sumsq_dev), stream()), "vptr_optim_prepare")
+            return
         check(lib.vptr_optim_prepare_accum(ptr(self.hyper), ptr(self.state), ptr(self.window), ptr(step_dev), ptr(sumsq_dev), stream()),
               "vptr_optim_prepare_accum")
         if not torch.cuda.is_current_stream_capturing():
             self.advance_mirror()
 
-    def adamw_ema(self, p, g, m, v, ema, n):
-        check(lib.vptr_adamw_ctl_ema(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), n, ptr(self.state), ptr(self.window), stream()), "vptr_adamw_ctl_ema")
+    def update(self, p, g, m, v, n, ema=None, groups=None):
+        """the clip + AdamW launch on the scalars `prepare` left; ema: the EMA slab (needs the window), groups: a `GroupTable`"""
+        if groups is not None:
+            check(lib.vptr_adamw_groups(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(groups.gid), n, ptr(self.state),
+                                        ptr(self.window) if ema is not None else None, ptr(groups.gstate), groups.ngroups, stream()), "vptr_adamw_groups")
+        elif ema is not None:
+            check(lib.vptr_adamw_ctl_ema(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), n, ptr(self.state), ptr(self.window), stream()), "vptr_adamw_ctl_ema")
+        else:
+            check(lib.vptr_adamw_ctl(ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(self.state), stream()), "vptr_adamw_ctl")
 
-    def prepare(self, step_dev, sumsq_dev):
-        check(lib.vptr_optim_prepare(ptr(self.hyper), ptr(self.state), ptr(step_dev), ptr(sumsq_dev), stream()), "vptr_optim_prepare")
 
-    def adamw(self, p, g, m, v, n):
-        check(lib.vptr_adamw_ctl(ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(self.state), stream()), "vptr_adamw_ctl")
-
-
-# ---- parameter groups (include/vptr_hip_groups.h, csrc/param_groups.hip) ------------------------------------------------------------
+# ---- parameter groups (include/vptr_hip_groups.h, csrc/optim.hip) -------------------------------------------------------------------
 def resolve_param_groups(params, param_groups):
     """`FlatAdamW(param_groups=...)` against the optimizer's parameter list -> (group index of every parameter, [(lr_scale, weight_decay
     or None)] per group).  Each entry is a dict {"params": [...], "lr_scale": 1.0, "weight_decay": None}; None inherits the optimizer's
@@ -367,8 +375,8 @@ def no_decay_groups(module, weight_decay=0.0):
 
 
 class GroupTable:
-    """The group map and the two group tables of one optimizer (include/vptr_hip_groups.h) and the launches on them.  `ghyper` is written
-    by the host only, one fill kernel per changed word, as `OptimControls._put` writes `hyper`; `gstate` by the device only."""
+    """The group map and the two group tables of one optimizer (include/vptr_hip_groups.h) and the launch that fills `gstate`; the update
+    on them is `OptimControls.update(groups=)`.  `ghyper` is written by the host only (a `Record`); `gstate` by the device only."""
 
     def __init__(self, device, gid, specs, default_weight_decay):
         """gid: uint8 CPU tensor, one group index per slab element; specs: [(lr_scale, weight_decay or None)]"""
@@ -380,19 +388,11 @@ class GroupTable:
         self.gid = gid.to(device).contiguous()
         buf = torch.zeros(2 * MAX_GROUPS * G_WORDS, device=device, dtype=torch.float32)
         self.ghyper, self.gstate = buf[:MAX_GROUPS * G_WORDS], buf[MAX_GROUPS * G_WORDS:]
-        if self.ghyper.data_ptr() % 64 or self.gstate.data_ptr() % 64:
-            raise RuntimeError("optimizer controls: the allocator returned a group table that is not 64-byte aligned")
-        self._host = [None] * (MAX_GROUPS * G_WORDS)
+        self._put = Record(self.ghyper, "group table").put
         self.lr_scale, self.weight_decay = [1.0] * self.ngroups, [None] * self.ngroups     # weight_decay None: inherits the default
         self._default = _finite("weight_decay", default_weight_decay, 0.0)
         for g, (scale, wd) in enumerate(specs):
             self.set(g, scale, wd, inherit=wd is None)
-
-    def _put(self, idx, value):
-        value = _f32(value)
-        if self._host[idx] != value:
-            self.ghyper[idx:idx + 1].fill_(value)
-            self._host[idx] = value
 
     def _group(self, g):
         if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 0 <= g < self.ngroups:
@@ -423,10 +423,6 @@ class GroupTable:
         """0-dim fp32 device view: the rate group g used in the last applied step (0 before the first)"""
         return self.gstate[self._group(g) * G_WORDS + GS_LR]
 
-    # -- launches ---------------------------------------------------------------------------------------------------------------
     def scalars(self, state):
+        """lane g: group g's step size and decay from the scalars a prepare launch just left in `state`"""
         check(lib.vptr_optim_group_scalars(ptr(state), ptr(self.ghyper), ptr(self.gstate), self.ngroups, stream()), "vptr_optim_group_scalars")
-
-    def adamw(self, p, g, m, v, ema, n, state, window):
-        check(lib.vptr_adamw_groups(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(self.gid), n, ptr(state), ptr(window) if ema is not None else None,
-                                    ptr(self.gstate), self.ngroups, stream()), "vptr_adamw_groups")

@@ -248,7 +248,7 @@ class FlatAdamW:
     bit-identical to the uncontrolled optimizer's.  Without controls nothing changes: the same three launches, the same state_dict.
 
     accum_steps (a whole number k >= 1) / ema_decay (0 <= d < 1): either one switches the controls on as well and adds their `window`
-    record (include/vptr_hip_accum.h, csrc/accum.hip).  Every `zero_grad()` + backward + `step()` is then one MICRO-step: `zero_grad`
+    record (include/vptr_hip_accum.h, csrc/optim.hip).  Every `zero_grad()` + backward + `step()` is then one MICRO-step: `zero_grad`
     zeroes the gradient slab only when a window of k micro-steps starts, `step` issues the same launches every time, and the update
     happens in the call that closes the window, on the sum of the window's gradients times grad_scale / k; the calls before it (holds)
     leave parameters, moments, step count and schedule position bit for bit as they are.  `applied()` tells which kind a call was.
@@ -257,7 +257,7 @@ class FlatAdamW:
     accum_steps=None is k = 1 without the window record.
 
     param_groups (a list of {"params": [...], "lr_scale": 1.0, "weight_decay": None}): switches the controls on as well and adds the
-    group map and group tables (include/vptr_hip_groups.h, csrc/param_groups.hip): torch.optim.AdamW with several param_groups under one
+    group map and group tables (include/vptr_hip_groups.h, csrc/optim.hip): torch.optim.AdamW with several param_groups under one
     LambdaLR and one clip_grad_norm_ over all parameters.  Group g steps with base_lr * lr_scale_g * schedule factor and its own
     weight decay (None inherits the optimizer's and follows `set_weight_decay`); the clip norm, betas and eps stay global.  Parameters
     that no entry lists form group 0 with the defaults, the listed groups follow (optim.resolve_param_groups).  lr_scale 0 leaves a
@@ -649,13 +649,9 @@ class FlatAdamW:
         if self.ctl is not None:
             # sumsq -> prepare (skip decision, step count, schedule, update scalars: one lane) -> the update reading them -> plane refresh.
             # A skipped step still refreshes the planes: they are rebuilt from unchanged weights.
-            if self._windowed:
-                self.ctl.set_grad_scale(grad_scale / self.ctl.accum_steps)
-                self.ctl.prepare_accum(self.step_dev, self.sumsq)
-            else:
-                self.ctl.set_grad_scale(grad_scale)
-                self.ctl.prepare(self.step_dev, self.sumsq)
-            if self.groups is not None:   # lane g: group g's step size and decay from the scalars the prepare launch just left
+            self.ctl.set_grad_scale(grad_scale / self.accum_steps)
+            self.ctl.prepare(self.step_dev, self.sumsq)
+            if self.groups is not None:
                 self.groups.scalars(self.ctl.state)
         else:
             self.step_dev.add_(1.0)
@@ -663,12 +659,8 @@ class FlatAdamW:
         if prof is not None:   # bench.py's HBM roofline pass: HIP events on the launch stream around the optimizer's streaming kernels
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record()
-        if self.groups is not None:
-            self.groups.adamw(self.flat, self.grad, self.m, self.v, self.ema, n, self.ctl.state, self.ctl.window)
-        elif self.ema is not None:
-            self.ctl.adamw_ema(self.flat, self.grad, self.m, self.v, self.ema, n)
-        elif self.ctl is not None:
-            self.ctl.adamw(self.flat, self.grad, self.m, self.v, n)
+        if self.ctl is not None:
+            self.ctl.update(self.flat, self.grad, self.m, self.v, n, self.ema, self.groups)
         else:
             check(lib.vptr_adamw(ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v), n, self.lr, self.betas[0], self.betas[1],
                                  self.eps, self.weight_decay, ptr(self.step_dev),
