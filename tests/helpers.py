@@ -857,3 +857,102 @@ def gemm_p16_class(fields, cus):
     if f("atomic") or not vec_ok:
         return (0, nst, "serial")
     return (0, nst, "batched" if nst == 4 else "rows_halves")
+
+
+# ---- the 7x7 end convolutions through the C ABI (tests/test_09k_conv7_abi_gpu.py): the launchers' selection arithmetic of csrc/conv7.hip restated
+CONV7_CLASSES = (
+    "in_fwd/fwd2", "in_fwd/fwd2c", "in_fwd/fwd2c_attr", "in_fwd/gen1", "in_fwd/reject",
+    "in_fwd_planes/fwd2", "in_fwd_planes/fwd2c", "in_fwd_planes/fwd2c_attr", "in_fwd_planes/reject",
+    "in_bwd_weight/chunks", "in_bwd_weight/one_wg", "in_bwd_weight/reject",
+    "out_fwd/fwd2", "out_fwd/gen1", "out_fwd/reject",
+    "out_bwd_data/data2", "out_bwd_data/gen1", "out_bwd_data/reject",
+    "out_bwd_weight/fpb4", "out_bwd_weight/fpb16", "out_bwd_weight/reject",
+    "out_bwd_weight_ws/ws", "out_bwd_weight_ws/ws_attr", "out_bwd_weight_ws/fallback", "out_bwd_weight_ws/reject",
+)
+
+
+def conv7_class(op, **g):
+    """the launch class of a call of csrc/conv7.hip, restated from its launchers.  Geometry keywords: B, Cimg, H, W and, where the entry point
+    takes them, Cout / Cin (default 64), aligned (the plane buffer on 128 bytes, the workspace on 16; default True), deterministic (default
+    False), ws_floats (None = a NULL workspace; default: exactly vptr_conv7_out_bwd_weight_workspace).  Returns {"class": one of CONV7_CLASSES}
+    plus what the class walks:
+    in_fwd / in_fwd_planes  fwd2: bands of 8 rows, rows of the last band; fwd2c: the same, 64-column chunks, quads of the last chunk (nq), dynamic
+                            LDS bytes (fwd2c_attr: above 64 KB, the launcher raises the kernel's limit); gen1: workgroups of 64 pixels, pixels of
+                            the last one;
+    in_bwd_weight           chunks of 2048 pixels, pixels of the last one (deterministic: one workgroup);
+    out_fwd                 fwd2: 4 x 16 patches, grid (x, Cimg), live waves of the last workgroup; gen1: 2 x 8 patches, the same;
+    out_bwd_data            data2: bands of 8 rows, rows of the last band, LDS bytes; gen1: 16-channel groups per pixel (ngrp), pixels per workgroup;
+    out_bwd_weight          frames per workgroup (fpb 4 / 16), grid y, frames of the last one;
+    out_bwd_weight_ws       ws: partials (3 per frame), LDS bytes (ws_attr: above 64 KB); fallback: the reason and the plain call's class."""
+    cdiv = lambda a, b: (a + b - 1) // b
+    B, Cimg, H, W = g["B"], g["Cimg"], g["H"], g["W"]
+    rej = {"class": op + "/reject"}
+    if op in ("in_fwd", "in_fwd_planes"):
+        planes = op == "in_fwd_planes"
+        if planes:
+            if not (B > 0 and 1 <= Cimg <= 4 and H > 3 and W > 3 and W % 4 == 0 and W <= (1024 if Cimg == 1 else 512) and g.get("Cout", 64) == 64) \
+                    or not g.get("aligned", True):
+                return rej
+        elif not (B > 0 and Cimg > 0 and H > 3 and W > 3) or g.get("Cout", 64) != 64:
+            return rej
+        bands = cdiv(H, 8)
+        walk = {"bands": B * bands, "last_band_rows": H - 8 * (bands - 1)}
+        if Cimg == 1 and W % 4 == 0 and W <= 1024:
+            return dict(walk, **{"class": op + "/fwd2", "lds": 4 * 14 * (W + 8)})
+        if Cimg <= 4 and W % 4 == 0 and W <= 512:
+            lds = 4 * Cimg * 14 * (W + 8)
+            return dict(walk, **{"class": op + ("/fwd2c_attr" if lds > 65536 else "/fwd2c"), "lds": lds, "chunks": cdiv(W, 64),
+                                 "last_nq": min(16, (W - 64 * (cdiv(W, 64) - 1)) // 4)})
+        if 4 * Cimg * 49 * 64 > 65536:
+            return rej
+        npix = B * H * W
+        return {"class": op + "/gen1", "blocks": cdiv(npix, 64), "last_pixels": npix - 64 * (cdiv(npix, 64) - 1)}
+    if op == "in_bwd_weight":
+        if not (B > 0 and Cimg > 0 and H > 3 and W > 3) or g.get("Cout", 64) != 64:
+            return rej
+        npix = B * H * W
+        if g.get("deterministic", False):
+            return {"class": op + "/one_wg", "chunks": 1, "last_pixels": npix}
+        return {"class": op + "/chunks", "chunks": cdiv(npix, 2048), "last_pixels": npix - 2048 * (cdiv(npix, 2048) - 1)}
+    Cin = g.get("Cin", 64)
+    if op == "out_fwd":
+        if not (B > 0 and H > 3 and W > 3 and Cimg > 0) or Cin != 64:
+            return rej
+        if Cimg <= 4 and H % 4 == 0 and W % 16 == 0:
+            patches = B * (H // 4) * (W // 16)
+            return {"class": op + "/fwd2", "grid": (cdiv(patches, 4), Cimg), "last_waves": patches - 4 * (cdiv(patches, 4) - 1)}
+        if 4 * Cimg * 49 * 64 > 65536:
+            return rej
+        patches = B * ((H + 1) // 2) * ((W + 7) // 8)
+        return {"class": op + "/gen1", "grid": (cdiv(patches, 4), 1), "last_waves": patches - 4 * (cdiv(patches, 4) - 1)}
+    if op == "out_bwd_data":
+        if not (B > 0 and Cin > 0 and Cin % 16 == 0 and 256 % (Cin // 16) == 0 and H > 6 and W > 6 and Cimg > 0):
+            return rej
+        lds2 = 4 * Cimg * (H + 12) * 80
+        if Cimg <= 4 and Cin == 64 and W == 64 and lds2 <= 80 * 1024:
+            bands = cdiv(H, 8)
+            return {"class": op + "/data2", "bands": B * bands, "last_band_rows": H - 8 * (bands - 1), "lds": lds2}
+        if 4 * Cimg * 49 * Cin > 65536:
+            return rej
+        ppb = 256 // (Cin // 16)
+        return {"class": op + "/gen1", "ngrp": Cin // 16, "pixels_per_wg": ppb, "blocks": cdiv(B * H * W, ppb)}
+
+    def plain():
+        if not (B > 0 and Cin == 64 and H % 8 == 0 and W % 8 == 0 and 1 <= Cimg <= 3):
+            return {"class": "out_bwd_weight/reject"}
+        fpb = 16 if B >= 64 else 4
+        return {"class": "out_bwd_weight/fpb%d" % fpb, "fpb": fpb, "grid": ((H // 8) * (W // 8), cdiv(B, fpb)), "last_frames": B - fpb * (cdiv(B, fpb) - 1)}
+    if op == "out_bwd_weight":
+        return plain()
+    assert op == "out_bwd_weight_ws", op
+    need = B * 3 * Cimg * 49 * 64
+    GW = 4 * ((W + 6 + 3) // 4) + 8
+    lds = max(4 * (cdiv(H + 6, 3) + 1 + 6) * GW, 4 * 4 * 49 * 64)
+    ws_floats = g.get("ws_floats", need)
+    reason = ("null" if ws_floats is None else "short" if ws_floats < need else "lds" if lds > 150 * 1024 else "small" if H < 8 or W < 8 else None)
+    if reason:
+        p = plain()
+        return {"class": op + ("/fallback" if p["class"] != "out_bwd_weight/reject" else "/reject"), "reason": reason, "plain": p}
+    if not (B > 0 and Cin == 64 and 1 <= Cimg <= 3) or not g.get("aligned", True):
+        return rej
+    return {"class": op + ("/ws_attr" if lds > 65536 else "/ws"), "partials": 3 * B, "lds": lds}

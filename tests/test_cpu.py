@@ -1645,3 +1645,118 @@ def test_gemm_p16_cases_notice_mutations(mut, capsys):
     for cid in GEMM_P16_MUTATION_CASES[mut]:
         with pytest.raises(AssertionError):
             C.run_case(be, cid)
+
+
+# ---- the 7x7 end convolutions through the C ABI (tests/test_09k_conv7_abi_gpu.py): cases, launch classes, mutations
+def test_conv7_cases_land_in_their_launch_classes():
+    """the launchers' selection arithmetic restated (helpers.conv7_class): every case of tests/conv7_cases.py reaches the class it names (asserted
+    by the runner as well, case by case), every class is reached, and the walks the cases were chosen for are the ones they take"""
+    import conv7_cases as C
+    from helpers import CONV7_CLASSES, conv7_class
+    census = C.class_census()
+    assert set(census) == set(CONV7_CLASSES), sorted(set(census) ^ set(CONV7_CLASSES))
+    for (B, Cimg, H, W), c in C.IN_FWD.items():
+        assert conv7_class("in_fwd", B=B, Cimg=Cimg, H=H, W=W)["class"] == "in_fwd/" + c
+    for (B, Cimg, H, W), c in C.IN_PLANES.items():
+        assert conv7_class("in_fwd_planes", B=B, Cimg=Cimg, H=H, W=W)["class"] == "in_fwd_planes/" + c
+    for (B, Cimg, H, W), c in C.OUT_FWD.items():
+        assert conv7_class("out_fwd", B=B, Cimg=Cimg, H=H, W=W)["class"] == "out_fwd/" + c
+    for (B, Cimg, H, W, Cin), c in C.OUT_DX.items():
+        assert conv7_class("out_bwd_data", B=B, Cimg=Cimg, H=H, W=W, Cin=Cin)["class"] == "out_bwd_data/" + c
+    for (B, Cimg, H, W), c in C.OUT_DW.items():
+        assert conv7_class("out_bwd_weight", B=B, Cimg=Cimg, H=H, W=W)["class"] == "out_bwd_weight/" + c
+    for (B, Cimg, H, W), c in C.OUT_WS.items():
+        assert conv7_class("out_bwd_weight_ws", B=B, Cimg=Cimg, H=H, W=W)["class"] == "out_bwd_weight_ws/" + c
+
+    def k(op, B, Cimg, H, W, **kw):
+        return conv7_class(op, B=B, Cimg=Cimg, H=H, W=W, **kw)
+    # conv7_in: a second band of one row; nq = 16; a second chunk of one quad; three chunks; the LDS sizes past 64 KB; partial last workgroups
+    assert k("in_fwd", 1, 1, 9, 8)["last_band_rows"] == 1
+    assert (k("in_fwd", 2, 3, 8, 64)["chunks"], k("in_fwd", 2, 3, 8, 64)["last_nq"]) == (1, 16)
+    assert (k("in_fwd", 1, 3, 8, 68)["chunks"], k("in_fwd", 1, 3, 8, 68)["last_nq"]) == (2, 1)
+    assert k("in_fwd", 1, 3, 5, 132)["chunks"] == 3
+    assert k("in_fwd", 1, 3, 4, 384)["lds"] == 65856 and k("in_fwd", 1, 3, 4, 380)["class"] == "in_fwd/fwd2c"
+    assert k("in_fwd", 1, 4, 4, 288)["lds"] == 66304 and k("in_fwd", 1, 4, 4, 284)["class"] == "in_fwd/fwd2c"
+    assert k("in_fwd", 1, 4, 4, 512)["lds"] == 116480
+    assert k("in_fwd", 1, 1, 9, 11)["last_pixels"] == 35 and k("in_fwd", 3, 3, 5, 7)["last_pixels"] == 41
+    assert [k("in_bwd_weight", *g)["last_pixels"] for g in ((1, 1, 23, 89), (1, 1, 32, 64), (1, 1, 25, 82), (2, 1, 25, 82))] == [2047, 2048, 2, 4]
+    assert [k("in_bwd_weight", *g)["chunks"] for g in ((1, 1, 23, 89), (1, 1, 32, 64), (1, 1, 25, 82), (2, 1, 25, 82))] == [1, 1, 2, 3]
+    assert not any(h > 3 and 2049 % h == 0 and 2049 // h > 3 for h in range(1, 2050))       # why 2050 stands in for 2049
+    # conv7_out_fwd: three patches in one partial workgroup, gridDim.y = 3
+    assert k("out_fwd", 3, 3, 4, 16)["grid"] == (1, 3) and k("out_fwd", 3, 3, 4, 16)["last_waves"] == 3
+    # conv7_out_bwd_data: partial bands, the LDS limit between H = 73 and 74, ngrp 2 / 4 / 8
+    assert [k("out_bwd_data", 1, 1, h, 64)["last_band_rows"] for h in (7, 8, 9, 20)] == [7, 8, 1, 4]
+    assert k("out_bwd_data", 1, 3, 73, 64)["lds"] == 81600 and k("out_bwd_data", 1, 3, 74, 64)["class"] == "out_bwd_data/gen1"
+    assert [k("out_bwd_data", 1, 2, 8, 8, Cin=c)["ngrp"] for c in (32, 64, 128)] == [2, 4, 8]
+    # weight gradients: ragged frame groups; 3 - 33 partials; the attribute branch and the 150 KB fallback
+    assert [k("out_bwd_weight", *g)["last_frames"] for g in C.OUT_DW] == [1, 1, 16, 1]
+    assert sorted(k("out_bwd_weight_ws", *g)["partials"] for g in C.OUT_WS if g[1:] == (1, 8, 8)) == [3, 12, 15, 18, 33]
+    assert k("out_bwd_weight_ws", 1, 1, 8, 2048)["lds"] == 99072 and k("out_bwd_weight_ws", 1, 1, 8, 4096)["reason"] == "lds"
+
+
+@pytest.mark.parametrize("part", range(4))
+def test_conv7_cases_against_emulation(part, capsys):
+    """every case of tests/test_09k_conv7_abi_gpu.py against the fp64 CPU emulation of the calls: argument orders, layouts, guards, references
+    and bars of the CASES"""
+    import conv7_cases as C
+    be = C.EmuBackend()
+    if part == 0:
+        for g in C.IN_FWD:
+            for s in (True, False):
+                C.run_in_fwd(be, g, s)
+        C.run_in_fwd_rejects(be)
+        for g in C.IN_PLANES:
+            C.run_in_planes(be, g)
+        C.run_in_planes_rejects(be)
+    elif part == 1:
+        for c in C.in_dw_cases():
+            C.run_in_dw(be, *c)
+        C.run_in_dw_rejects(be)
+        for g in C.OUT_FWD:
+            m = C.run_out_fwd(be, g)
+            assert max(m.values()) <= 2.0 ** -23        # the emulation's activations are fp64 values rounded once
+        C.run_out_fwd_rejects(be)
+    elif part == 2:
+        for g in C.OUT_DX:
+            for a in C.ACTS:
+                C.run_out_dx(be, g, a)
+        C.run_out_dx_rejects(be)
+    else:
+        for g in C.OUT_DW:
+            for a in C.ACTS:
+                C.run_out_dw(be, g, a)
+        C.run_out_dw_rejects(be)
+        for g in C.OUT_WS:
+            for det in (0, 1):
+                C.run_out_ws(be, g, C.TANH if det else C.SIGMOID, det)
+        C.run_out_ws(be, (2, 3, 9, 11), C.NONE, 0, with_db=False)
+        for name in C.OUT_WS_FALLBACKS:
+            C.run_out_ws_fallback(be, name)
+        C.run_out_ws_rejects(be)
+
+
+# mutation of the emulation -> cases that have to notice it (every one listed must fail)
+CONV7_MUTATION_CASES = {
+    "replicate": [("run_in_fwd", (2, 1, 4, 4), False), ("run_out_fwd", (1, 1, 4, 16)), ("run_out_dx", (2, 1, 7, 7, 64), 0), ("run_out_ws", (2, 3, 9, 11), 1, 0),
+                  ("run_in_dw", 1, 1, 23, 89, 0)],
+    "dx_fold_dropped": [("run_out_dx", (1, 1, 7, 64, 64), 1), ("run_out_dx", (2, 1, 7, 7, 64), 0)],
+    "kykx_swapped": [("run_in_fwd", (1, 1, 9, 11), True), ("run_in_planes", (1, 3, 8, 68)), ("run_out_fwd", (2, 3, 9, 11)), ("run_out_dx", (1, 3, 9, 64, 64), 2),
+                     ("run_out_dw", (1, 1, 8, 8), 1), ("run_in_dw", 1, 3, 32, 64, 1)],
+    "sigmoid_grad_dy": [("run_out_dx", (1, 1, 8, 64, 64), 2), ("run_out_dw", (5, 3, 8, 16), 2), ("run_out_ws", (1, 1, 8, 8), 2, 0)],
+    "dw_overwritten": [("run_out_dw", (1, 1, 8, 8), 0), ("run_out_ws", (4, 1, 8, 8), 1, 1), ("run_out_ws_fallback", "null"), ("run_in_dw", 1, 1, 25, 82, 0)],
+    "planes_swapped": [("run_in_planes", (2, 1, 4, 4)), ("run_in_planes", (1, 3, 4, 384))],
+    "chunk_off_by_quad": [("run_in_fwd", (1, 3, 8, 68), True), ("run_in_fwd", (1, 3, 5, 132), False), ("run_in_planes", (1, 3, 8, 68))],
+}
+
+
+@pytest.mark.parametrize("mut", sorted(CONV7_MUTATION_CASES))
+def test_conv7_cases_notice_mutations(mut, capsys):
+    """each named defect of the emulation -- replicate instead of reflect, the top border's mirror fold missing from dx, ky and kx swapped, the
+    sigmoid's gradient taken from dy alone, dw overwritten instead of accumulated, the hi / lo plane halves swapped, the 64-column chunk boundary
+    one quad early -- makes every case listed for it fail (and the unmutated emulation passes them, above)"""
+    import conv7_cases as C
+    assert sorted(CONV7_MUTATION_CASES) == sorted(C.MUTATIONS)
+    be = C.EmuBackend(mut=mut)
+    for fn, *args in CONV7_MUTATION_CASES[mut]:
+        with pytest.raises(AssertionError):
+            getattr(C, fn)(be, *args)

@@ -212,7 +212,10 @@ extern "C" int vptr_conv7_in_fwd(const float* x, const float* w, const float* sc
   }
   if (Cimg <= 4 && W % 4 == 0 && W <= 512) {   // colour images (BAIR): the row-wide variant of the same kernel
     const int rpw = 8, bands = (H + rpw - 1) / rpw;
-    conv7_in_fwd2c_kernel<<<B * bands, 256, sizeof(float) * Cimg * (rpw + 6) * (W + 8), (hipStream_t)stream>>>(x, w, scale, shift, y, B, Cimg, H, W, rpw, 0);
+    const size_t lds2c = sizeof(float) * Cimg * (rpw + 6) * (W + 8);   // up to 116 480 bytes (Cimg = 4, W = 512)
+    if (lds2c > 64 * 1024)
+      (void)hipFuncSetAttribute((const void*)conv7_in_fwd2c_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2c);
+    conv7_in_fwd2c_kernel<<<B * bands, 256, lds2c, (hipStream_t)stream>>>(x, w, scale, shift, y, B, Cimg, H, W, rpw, 0);
     VPTR_LAUNCH_CHECK();
     return 0;
   }
@@ -233,8 +236,10 @@ extern "C" int vptr_conv7_in_fwd_planes(const float* x, const float* w, const fl
   VPTR_CHECK((reinterpret_cast<uintptr_t>(planes) & 127) == 0, "conv7_in_fwd_planes: the plane buffer must be 128-byte aligned");
   const int rpw = 8, bands = (H + rpw - 1) / rpw;
   if (Cimg > 1) {
-    conv7_in_fwd2c_kernel<<<B * bands, 256, sizeof(float) * Cimg * (rpw + 6) * (W + 8), (hipStream_t)stream>>>(x, w, scale, shift, reinterpret_cast<float*>(planes), B,
-                                                                                                             Cimg, H, W, rpw, 1);
+    const size_t lds2c = sizeof(float) * Cimg * (rpw + 6) * (W + 8);
+    if (lds2c > 64 * 1024)
+      (void)hipFuncSetAttribute((const void*)conv7_in_fwd2c_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2c);
+    conv7_in_fwd2c_kernel<<<B * bands, 256, lds2c, (hipStream_t)stream>>>(x, w, scale, shift, reinterpret_cast<float*>(planes), B, Cimg, H, W, rpw, 1);
     VPTR_LAUNCH_CHECK();
     return 0;
   }
