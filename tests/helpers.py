@@ -414,14 +414,18 @@ def ts_attn_ref(q, k, v, go, N, Tq, Tk, H, W, ws, nh, mask=None):
                      False, mask, 1.0)
 
 
+def split_bf16(x):
+    """the hi / lo split of the split-bf16 kernels (split2 of csrc/gemm_shared.h, the P16 format): hi = bf16_rne(x), lo = bf16_rne(x - hi), both bf16"""
+    hi = x.to(torch.bfloat16)
+    return hi, (x - hi.float()).to(torch.bfloat16)
+
+
 def p16_encode(x):
     """fp32 [rows, C] (C % 16 == 0) -> the P16 tensor of the same shape and dtype with plain torch ops: per 16-channel granule 16 bf16 hi
     (round to nearest even of x) followed by 16 bf16 lo = bf16(x - hi); the inverse of ops.core.p16_decode up to 2^-17 relative per element"""
     C = x.shape[-1]
     assert C % 16 == 0 and x.dtype == torch.float32
-    g = x.contiguous().reshape(-1, C // 16, 16)
-    hi = g.to(torch.bfloat16)
-    lo = (g - hi.float()).to(torch.bfloat16)
+    hi, lo = split_bf16(x.contiguous().reshape(-1, C // 16, 16))
     return torch.stack([hi, lo], 2).reshape(-1).view(torch.float32).reshape(x.shape)
 
 
@@ -857,6 +861,137 @@ def gemm_p16_class(fields, cus):
     if f("atomic") or not vec_ok:
         return (0, nst, "serial")
     return (0, nst, "batched" if nst == 4 else "rows_halves")
+
+
+# ---- the fp32-staged GEMM through the C ABI (tests/test_01c_gemm_f32_abi_gpu.py): vptr_gemm's host decisions restated
+GEMM_F32_MIN_TILES = 384      # kV4MinTiles of csrc/gemm.hip: grids below it take the pipelined loop
+
+
+def gemm_f32_nfn(N):
+    """nfn_for (csrc/gemm.hip): column fragments of the tile, exact 176-wide tiles when they divide N, else least padding"""
+    if N % 176 == 0:
+        return 11
+    if N <= 64:
+        return 4
+    if N <= 128:
+        return 8
+    w11, w8, w4 = -(-N // 176) * 176, -(-N // 128) * 128, -(-N // 64) * 64
+    nfn, best = 11, w11
+    if w8 < best:
+        best, nfn = w8, 8
+    if w4 < best:
+        best, nfn = w4, 4
+    return nfn
+
+
+def gemm_f32_plan(fields):
+    """k_chunk, splits, NFN, tiles_m, tiles_n and the grid size exactly as vptr_gemm computes them (after its checks)"""
+    f = lambda k: fields.get(k, 0) or 0
+    split_k, batch = max(f("split_k"), 1), max(f("batch"), 1)
+    M, N, K = f("M"), f("N"), f("K")
+    k_chunk = -(-(-(-K // split_k)) // 32) * 32
+    splits = -(-K // k_chunk)
+    nfn = gemm_f32_nfn(N)
+    tiles_m, tiles_n = -(-M // 128), -(-N // (16 * nfn))
+    return dict(k_chunk=k_chunk, splits=splits, nfn=nfn, tiles_m=tiles_m, tiles_n=tiles_n, batch=batch, grid=tiles_m * tiles_n * splits * batch)
+
+
+def gemm_f32_class(fields):
+    """the launch class of a vptr_gemm call with fp32-staged operands (a_mode 0 .. 2, b_mode 0 / 1), restated from vptr_gemm, launch_one and the
+    epilogue choice of the two kernels (csrc/gemm.hip).  fields: vptr_gemm_desc members by name, pointers as integer addresses (0 / missing =
+    NULL), everything missing = 0.  Returns (loop, epilogue, NFN, A stager, B stager, NPASS) with loop "P" (vptr_gemm_kernel_p) or "S"
+    (vptr_gemm_kernel), epilogue "rows", "frag" (gemm_epilogue<NFN, 1>), "rows_halves" or "serial", the stagers "kc", "ks2", "conv" / "kc", "ks";
+    or ("refuse", k) with k the VPTR_CHECK of vptr_gemm that refuses the descriptor, counted from 1 at the empty-problem check in source order
+    over the checks these operands can reach (30 = launch_modes' unsupported mode pair).  No device property enters the decision."""
+    f = lambda k: fields.get(k, 0) or 0
+
+    def bits(*ks):
+        v = 0
+        for k in ks:
+            v |= int(f(k))
+        return v
+    M, N, K, am, bm = f("M"), f("N"), f("K"), f("a_mode"), f("b_mode")
+    if not (M > 0 and N > 0 and K > 0):
+        return ("refuse", 1)
+    if not (f("A") and f("B") and (f("D") or f("D_planes"))):
+        return ("refuse", 2)
+    if f("D_planes") and am != 3:
+        return ("refuse", 3)
+    if f("precision") not in (1, 3):
+        return ("refuse", 4)
+    if f("batch_accum") or f("batch_stride_d"):
+        return ("refuse", 5)
+    if f("d_p16"):
+        return ("refuse", 6)
+    split_in = f("split_k")
+    if (f("d_row_w") > 0 or f("d_row_off") != 0) and not (f("d_row_w") > 0 and am <= 2 and not f("residual") and not f("Dpre") and f("batch") <= 1
+                                                         and not f("atomic") and split_in <= 1):
+        return ("refuse", 7)
+    if f("act_grad_src") or f("frame_stats"):
+        return ("refuse", 8)
+    if am == 4:
+        return ("refuse", 9)
+    if bits("A", "B") & 15:
+        return ("refuse", 10)
+    if not (am == 1 and bm == 1) and K % 4:
+        return ("refuse", 11)
+    if am == 0 and f("lda") % 4:
+        return ("refuse", 12)
+    if am == 1 and (f("lda") % 4 or M % 4):
+        return ("refuse", 13)
+    if bm == 0 and f("ldb") % 4:
+        return ("refuse", 14)
+    if bm == 1 and (f("ldb") % 4 or N % 4):
+        return ("refuse", 15)
+    if am == 2:
+        if f("conv_Cin") % 4:
+            return ("refuse", 16)
+        if K != f("conv_KH") * f("conv_KW") * f("conv_Cin"):
+            return ("refuse", 17)
+        if not (f("conv_stride") >= 1 and f("conv_OH") > 0 and f("conv_OW") > 0):
+            return ("refuse", 18)
+    split_k = max(split_in, 1)
+    p = f("dropout_p")
+    if split_k > 1 and not (f("act") == 0 and not f("act_after") and p == 0 and not f("rowscale") and not f("Dpre")):
+        return ("refuse", 19)
+    if p > 0 and not (f("seed_dev") and p < 1):
+        return ("refuse", 20)
+    if f("rowscale") and not (f("rs_div") >= 1 and f("rs_mod") >= 1):
+        return ("refuse", 21)
+    batch, ksegs = max(f("batch"), 1), max(f("ksegs"), 1)
+    if not (batch <= 3 and ksegs <= 3):
+        return ("refuse", 22)
+    if batch > 1 or ksegs > 1:
+        if not (batch == 1 or ksegs == 1):
+            return ("refuse", 23)
+        if not (split_k == 1 and am != 2 and not f("a_rowsum")):
+            return ("refuse", 24)
+        extra = (batch if batch > 1 else ksegs) - 1
+        if not (f("A_x1") and f("B_x1") and not bits("A_x1", "B_x1") & 15):
+            return ("refuse", 25)
+        if extra > 1 and not (f("A_x2") and f("B_x2") and not bits("A_x2", "B_x2") & 15):
+            return ("refuse", 26)
+        if batch > 1 and not (f("D_x1") and (extra < 2 or f("D_x2"))):
+            return ("refuse", 27)
+        if batch > 1 and (f("Dpre") or f("residual") or f("atomic")):
+            return ("refuse", 28)
+    if f("a_rowsum") and am != 1:
+        return ("refuse", 29)
+    if not ((am, bm) in ((0, 0), (0, 1), (1, 1), (1, 0), (2, 0))):
+        return ("refuse", 30)
+    plan = gemm_f32_plan(fields)
+    loop = "P" if plan["grid"] < GEMM_F32_MIN_TILES or f("a_rowsum") else "S"
+    use_atomic = bool(f("atomic")) or (batch <= 1 and plan["splits"] > 1)
+    vbits = bits("D", "Dpre", "residual", "bias", "colscale")
+    if batch > 1:
+        vbits |= bits("D_x1", "D_x2", "bias_x1", "bias_x2")
+    vec_ok = (vbits & 15) == 0 and N % 4 == 0 and f("ldd") % 4 == 0 and f("ldr") % 4 == 0
+    rows = not use_atomic and vec_ok and f("d_row_w") == 0
+    if loop == "P":
+        epi = "rows" if rows else "frag"
+    else:
+        epi = "rows_halves" if plan["nfn"] == 11 and rows else "serial"
+    return (loop, epi, plan["nfn"], ("kc", "ks2", "conv")[am], ("kc", "ks")[bm], f("precision"))
 
 
 # ---- the 7x7 end convolutions through the C ABI (tests/test_09k_conv7_abi_gpu.py): the launchers' selection arithmetic of csrc/conv7.hip restated

@@ -1647,6 +1647,123 @@ def test_gemm_p16_cases_notice_mutations(mut, capsys):
             C.run_case(be, cid)
 
 
+# ---- the fp32-staged GEMM through the C ABI (tests/test_01c_gemm_f32_abi_gpu.py): the launch-class mirror, the census, the cases against a CPU
+# emulation of the call and the mutations of the emulation
+_F = dict(a_mode=0, b_mode=0, precision=3, M=300, N=528, K=144, lda=144, ldb=144, ldd=528, A=0x10000, B=0x20000, D=0x30000)      # 3 x 3 tiles of 128 x 176
+_FX = dict(A_x1=0x11000, B_x1=0x21000, D_x1=0x31000, A_x2=0x12000, B_x2=0x22000, D_x2=0x32000)
+_FC = dict(a_mode=2, K=36, conv_IH=8, conv_IW=8, conv_Cin=4, conv_OH=8, conv_OW=8, conv_KH=3, conv_KW=3, conv_stride=1, conv_pad=1)
+# written by hand from vptr_gemm, launch_one, nfn_for and the epilogue choice of the two kernels: (changes to _F, class)
+GEMM_F32_TABLE = [
+    (dict(), ("P", "rows", 11, "kc", "kc", 3)), (dict(precision=1), ("P", "rows", 11, "kc", "kc", 1)), (dict(M=128 * 128), ("S", "rows_halves", 11, "kc", "kc", 3)),
+    (dict(M=128 * 127 + 1), ("S", "rows_halves", 11, "kc", "kc", 3)), (dict(M=128 * 127), ("P", "rows", 11, "kc", "kc", 3)),      # 384 / 381 workgroups
+    (dict(M=128 * 128, N=527, ldd=528), ("S", "serial", 11, "kc", "kc", 3)),                    # N % 4 != 0
+    (dict(N=64, ldd=64), ("P", "rows", 4, "kc", "kc", 3)), (dict(N=50, ldd=52), ("P", "frag", 4, "kc", "kc", 3)), (dict(N=65, ldd=68), ("P", "frag", 8, "kc", "kc", 3)), (dict(N=128, ldd=128), ("P", "rows", 8, "kc", "kc", 3)),
+    (dict(N=180, ldd=180), ("P", "rows", 4, "kc", "kc", 3)), (dict(N=200, ldd=200), ("P", "rows", 8, "kc", "kc", 3)), (dict(N=340, ldd=340), ("P", "rows", 11, "kc", "kc", 3)),
+    (dict(N=129, ldd=132), ("P", "frag", 11, "kc", "kc", 3)), (dict(N=352, ldd=352), ("P", "rows", 11, "kc", "kc", 3)), (dict(N=384, ldd=384), ("P", "rows", 8, "kc", "kc", 3)),
+    (dict(M=128 * 384, N=64, ldd=64), ("S", "serial", 4, "kc", "kc", 3)), (dict(M=128 * 384, N=128, ldd=128, b_mode=1), ("S", "serial", 8, "kc", "ks", 3)),
+    (dict(ldd=530), ("P", "frag", 11, "kc", "kc", 3)), (dict(D=0x30004), ("P", "frag", 11, "kc", "kc", 3)), (dict(bias=0x40008), ("P", "frag", 11, "kc", "kc", 3)),
+    (dict(residual=0x50000, ldr=530), ("P", "frag", 11, "kc", "kc", 3)), (dict(Dpre=0x80004), ("P", "frag", 11, "kc", "kc", 3)), (dict(colscale=0x90004), ("P", "frag", 11, "kc", "kc", 3)),
+    (dict(M=128 * 128, D=0x30004), ("S", "serial", 11, "kc", "kc", 3)), (dict(M=128 * 128, atomic=1), ("S", "serial", 11, "kc", "kc", 3)),
+    (dict(atomic=1), ("P", "frag", 11, "kc", "kc", 3)), (dict(split_k=2), ("P", "frag", 11, "kc", "kc", 3)),
+    (dict(split_k=5), ("P", "frag", 11, "kc", "kc", 3)),                                        # k_chunk 32: 5 splits, 45 workgroups
+    (dict(K=100, lda=100, ldb=100, split_k=7, M=128 * 32), ("S", "serial", 11, "kc", "kc", 3)),  # the launcher makes 4 splits: 32 x 3 x 4 = 384
+    (dict(K=100, lda=100, ldb=100, split_k=7, M=128 * 31), ("P", "frag", 11, "kc", "kc", 3)),
+    (dict(K=100, lda=100, ldb=100, split_k=3, M=128 * 64), ("S", "serial", 11, "kc", "kc", 3)),  # k_chunk 64: 2 splits, 64 x 3 x 2 = 384
+    (dict(K=100, lda=100, ldb=100, split_k=3, M=128 * 63), ("P", "frag", 11, "kc", "kc", 3)),
+    (dict(a_mode=1, M=300, lda=300), ("P", "rows", 11, "ks2", "kc", 3)), (dict(a_mode=1, b_mode=1, M=300, lda=300, ldb=528, K=33), ("P", "rows", 11, "ks2", "ks", 3)),
+    (dict(a_mode=1, M=128 * 128, lda=128 * 128, a_rowsum=0xC0000), ("P", "rows", 11, "ks2", "kc", 3)),        # 384 workgroups, still pipelined
+    (dict(a_mode=1, M=128 * 128, lda=128 * 128), ("S", "rows_halves", 11, "ks2", "kc", 3)),
+    (dict(_FC), ("P", "rows", 11, "conv", "kc", 3)), (dict(_FC, d_row_w=8, d_row_off=8), ("P", "frag", 11, "conv", "kc", 3)),
+    (dict(_FC, M=128 * 128, d_row_w=8), ("S", "serial", 11, "conv", "kc", 3)), (dict(d_row_w=10), ("P", "frag", 11, "kc", "kc", 3)),
+    (dict(batch=3, **_FX), ("P", "rows", 11, "kc", "kc", 3)), (dict(batch=3, bias_x2=0x41004, **_FX), ("P", "frag", 11, "kc", "kc", 3)),
+    (dict(batch=3, M=128 * 43, **_FX), ("S", "rows_halves", 11, "kc", "kc", 3)),                # 43 x 3 x 3 = 387
+    (dict(batch=2, M=128 * 64, D_x1=0x31004, A_x1=0x11000, B_x1=0x21000), ("S", "serial", 11, "kc", "kc", 3)),
+    (dict(ksegs=3, **_FX), ("P", "rows", 11, "kc", "kc", 3)), (dict(ksegs=2, M=128 * 128, D_x1=0x31004, A_x1=0x11000, B_x1=0x21000), ("S", "rows_halves", 11, "kc", "kc", 3)),
+    # refusals, in source order
+    (dict(K=0), ("refuse", 1)), (dict(M=-1), ("refuse", 1)), (dict(A=0), ("refuse", 2)), (dict(D=0), ("refuse", 2)), (dict(D_planes=0xD0000), ("refuse", 3)),
+    (dict(precision=2), ("refuse", 4)), (dict(batch_accum=1), ("refuse", 5)), (dict(batch_stride_d=16), ("refuse", 5)), (dict(d_p16=1), ("refuse", 6)),
+    (dict(d_row_off=4), ("refuse", 7)), (dict(d_row_w=8, residual=0x50000), ("refuse", 7)), (dict(d_row_w=8, split_k=2), ("refuse", 7)), (dict(d_row_w=8, atomic=1), ("refuse", 7)),
+    (dict(d_row_w=8, batch=2, **_FX), ("refuse", 7)), (dict(act_grad_src=0xA0000), ("refuse", 8)), (dict(frame_stats=0xB0000), ("refuse", 8)), (dict(a_mode=4), ("refuse", 9)),
+    (dict(A=0x10004), ("refuse", 10)), (dict(B=0x20008), ("refuse", 10)), (dict(K=142), ("refuse", 11)), (dict(a_mode=1, K=33), ("refuse", 11)), (dict(lda=146), ("refuse", 12)),
+    (dict(a_mode=1, M=302, lda=304), ("refuse", 13)), (dict(a_mode=1, lda=302), ("refuse", 13)), (dict(ldb=145), ("refuse", 14)), (dict(b_mode=1, ldb=530), ("refuse", 15)),
+    (dict(b_mode=1, N=50, ldb=52), ("refuse", 15)), (dict(_FC, conv_Cin=6, conv_KH=2, conv_KW=2, K=24), ("refuse", 16)), (dict(_FC, K=40), ("refuse", 17)),
+    (dict(_FC, conv_stride=0), ("refuse", 18)), (dict(_FC, conv_OW=0), ("refuse", 18)), (dict(split_k=2, act=1), ("refuse", 19)), (dict(split_k=2, Dpre=0x80000), ("refuse", 19)),
+    (dict(split_k=2, rowscale=0x60000, rs_div=1, rs_mod=1), ("refuse", 19)), (dict(dropout_p=0.1), ("refuse", 20)), (dict(dropout_p=1.0, seed_dev=0x70000), ("refuse", 20)),
+    (dict(rowscale=0x60000, rs_div=0, rs_mod=1), ("refuse", 21)), (dict(batch=4, **_FX), ("refuse", 22)), (dict(ksegs=4, **_FX), ("refuse", 22)), (dict(batch=2, ksegs=2, **_FX), ("refuse", 23)),
+    (dict(ksegs=2, split_k=2, **_FX), ("refuse", 24)), (dict(_FC, ksegs=2, **_FX), ("refuse", 24)), (dict(a_mode=1, M=300, lda=300, batch=2, a_rowsum=0xC0000, **_FX), ("refuse", 24)),
+    (dict(ksegs=2, A_x1=0x11000), ("refuse", 25)), (dict(ksegs=2, A_x1=0x11004, B_x1=0x21000), ("refuse", 25)), (dict(ksegs=3, A_x1=0x11000, B_x1=0x21000), ("refuse", 26)),
+    (dict(batch=2, A_x1=0x11000, B_x1=0x21000), ("refuse", 27)), (dict(batch=3, A_x1=0x11000, B_x1=0x21000, A_x2=0x12000, B_x2=0x22000, D_x1=0x31000), ("refuse", 27)),
+    (dict(batch=2, residual=0x50000, **_FX), ("refuse", 28)), (dict(batch=2, atomic=1, **_FX), ("refuse", 28)), (dict(a_rowsum=0xC0000), ("refuse", 29)),
+    (dict(_FC, a_rowsum=0xC0000), ("refuse", 29)), (dict(_FC, b_mode=1), ("refuse", 30)), (dict(b_mode=2), ("refuse", 30)),
+]
+
+
+def test_gemm_f32_class_table():
+    """helpers.gemm_f32_class against a table written by hand from vptr_gemm's checks, its split / tile arithmetic, launch_one's loop choice and
+    the kernels' epilogue choice; every (loop, epilogue, NFN) combination and every refusal appears in it"""
+    from helpers import gemm_f32_class, gemm_f32_plan
+    import gemm_f32_cases as C
+    bad = []
+    for change, want in GEMM_F32_TABLE:
+        got = gemm_f32_class(dict(_F, **change))
+        if got != want:
+            bad.append((change, got, want))
+    assert not bad, bad
+    assert {w[:3] for _, w in GEMM_F32_TABLE if w[0] != "refuse"} == set(C.LOOPS_EPIS)
+    assert {w[1] for _, w in GEMM_F32_TABLE if w[0] == "refuse"} == set(C.REJECTS) - {0}      # 0: the null descriptor, no fields to mirror
+    plan = gemm_f32_plan(dict(_F, K=100, split_k=7))
+    assert (plan["k_chunk"], plan["splits"], plan["grid"]) == (32, 4, 36)
+
+
+def test_gemm_f32_cases_census():
+    """the issue's census: the ten (loop, epilogue, NFN) combinations by two cases or more and once with the full epilogue option set at
+    precision 3; the five operand-mode pairs, both B stagers at every NFN and every stager at precision 1, in both loops; the named grid sizes"""
+    import gemm_f32_cases as C
+    census = C.class_census()
+    assert not C.census_gaps(census), C.census_gaps(census)
+    assert sum(len(v) for v in census.values()) == len(C.CASES)
+    assert {1, 3, 7, 9, 13, 385} <= {C.SPEC[n].get("grid") for n in C.CASES}
+
+
+GEMM_F32_PARTS = 8
+
+
+@pytest.mark.parametrize("part", range(GEMM_F32_PARTS))
+def test_gemm_f32_cases_against_emulation(part, capsys):
+    """every case of tests/test_01c_gemm_f32_abi_gpu.py against the fp32 CPU emulation of the call: descriptors, pitches, guards, references and
+    bars of the CASES; the emulation's fp32 arithmetic stays inside every bar, and the fp64 reference alone leaves at most 1 % of a case's
+    elements to the kink rule (asserted per case by the runner)"""
+    import gemm_f32_cases as C
+    be = C.EmuBackend()
+    for name in C.CASES[part::GEMM_F32_PARTS]:
+        _, figures = C.run_case(be, name)
+        assert all(w <= 1.0 for w, _ in figures)
+    if part == 0:
+        for k in C.REJECTS:
+            C.run_reject(be, k)
+
+
+# mutation -> cases that have to notice it (at least one each; every listed case must fail).  a_tail_unmasked: the kernel zeroes the K tail in A
+# only and leaves B's clamped loads in place, so the mutation accumulates the products of the two clamped tails
+GEMM_F32_MUTATION_CASES = {
+    "a_tail_unmasked": ["kc_K36", "kc_K4", "ksks_K33", "kskc_K36", "conv3s1_zero"], "reflect_off_by_one": ["conv3s1_reflect", "conv_map2x3", "conv_map3x2"],
+    "parity_dropped": ["convT_s2", "convT_s3"], "seg3_reads_seg2": ["kseg3_K48", "kseg3_ksks"], "d_row_off_ignored": ["subpixel_c12", "subpixel_c6"],
+    "bias_every_split": ["split2", "split7", "conv_split2"], "rowsum_clamped_rows": ["rowsum_tiles", "rowsum_split"],
+    "drop_index_ldd": ["full_rows4", "full_frag4", "rows_drop_nores"], "lo_dropped": ["kc_K68", "ksks_K65", "conv3s2_zero"],
+}
+
+
+@pytest.mark.parametrize("mut", sorted(GEMM_F32_MUTATION_CASES))
+def test_gemm_f32_cases_notice_mutations(mut, capsys):
+    """each named mutation of the emulation makes every case listed for it fail (and the unmutated emulation passes them, above)"""
+    import gemm_f32_cases as C
+    assert sorted(GEMM_F32_MUTATION_CASES) == sorted(C.MUTATIONS)
+    be = C.EmuBackend(mut=mut)
+    for name in GEMM_F32_MUTATION_CASES[mut]:
+        with pytest.raises(AssertionError):
+            C.run_case(be, name)
+
+
 # ---- the 7x7 end convolutions through the C ABI (tests/test_09k_conv7_abi_gpu.py): cases, launch classes, mutations
 def test_conv7_cases_land_in_their_launch_classes():
     """the launchers' selection arithmetic restated (helpers.conv7_class): every case of tests/conv7_cases.py reaches the class it names (asserted

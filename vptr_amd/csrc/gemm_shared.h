@@ -510,7 +510,8 @@ __device__ __forceinline__ void gemm_epilogue_serial(const vptr_gemm_desc& p, co
             if (p.Dpre) p.Dpre[(int64_t)row * p.ldd + col] = v;
             v = vptr_act(v, p.act);
             if (p.rowscale) v *= p.rowscale[(row / p.rs_div) % p.rs_mod];
-            if (p.dropout_p > 0.f) v *= vptr_drop_scale(seed, p.site, (uint64_t)row * (uint64_t)p.N + col, p.dropout_p);
+            // + 0: a dropped element is +0 like in the other epilogues, which always add the (zero) residual (x * 0 alone keeps the sign of x)
+            if (p.dropout_p > 0.f) v = v * vptr_drop_scale(seed, p.site, (uint64_t)row * (uint64_t)p.N + col, p.dropout_p) + 0.f;
             if (p.residual && first_split) v += p.residual[(int64_t)row * p.ldr + col];
             if (p.act_after) v = v > 0.f ? v : 0.f;
             float* dst = mb.D + epi_drow(p, row) * p.ldd + col;
