@@ -174,6 +174,11 @@ GROUP_SIGNATURES = {
     "vptr_optim_group_scalars": [P, P, P, I, P],
     "vptr_adamw_groups": [P, P, P, P, P, P, L, P, P, P, I, P],
 }
+# the HBM-resident clip store: batches drawn and gathered on the device, declared in include/vptr_hip_data.h (additive as well)
+DATA_SIGNATURES = {
+    "vptr_clip_draw": [P, P, P, I, I, I, I, I, F, F, P],
+    "vptr_clip_ingest_gather": [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P],
+}
 
 
 def _load():
@@ -182,7 +187,7 @@ def _load():
             "vptr_amd: %s is missing. Build it with `python -m vptr_amd.build` (needs hipcc, gfx950). "
             "There is no CPU / PyTorch fallback for the VPTR hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(GAN_SIGNATURES.items()) + list(GROUP_SIGNATURES.items()):
+    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(GAN_SIGNATURES.items()) + list(GROUP_SIGNATURES.items()) + list(DATA_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.argtypes = argt
         fn.restype = c_int
