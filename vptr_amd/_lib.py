@@ -179,6 +179,10 @@ DATA_SIGNATURES = {
     "vptr_clip_draw": [P, P, P, I, I, I, I, I, F, F, P],
     "vptr_clip_ingest_gather": [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P],
 }
+# per-tensor statistics of the optimizer's slabs (csrc/tensor_stats.hip), declared in include/vptr_hip_diag.h (additive as well)
+DIAG_SIGNATURES = {
+    "vptr_tensor_stats": [P, P, P, P, P, P, I, P, P, P, P, P, L, I, P],
+}
 
 
 def _load():
@@ -187,7 +191,7 @@ def _load():
             "vptr_amd: %s is missing. Build it with `python -m vptr_amd.build` (needs hipcc, gfx950). "
             "There is no CPU / PyTorch fallback for the VPTR hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(GAN_SIGNATURES.items()) + list(GROUP_SIGNATURES.items()) + list(DATA_SIGNATURES.items()):
+    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(GAN_SIGNATURES.items()) + list(GROUP_SIGNATURES.items()) + list(DATA_SIGNATURES.items()) + list(DIAG_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.argtypes = argt
         fn.restype = c_int

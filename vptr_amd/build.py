@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libvptr_hip.so")
-SOURCES = ["api.hip", "gemm.hip", "gemm_p16.hip", "layernorm.hip", "norm_act.hip", "dwconv.hip", "attn.hip", "attn_mfma.hip", "attn16.hip", "elementwise.hip", "conv7.hip", "losses.hip", "recon_loss.hip", "gan_loss.hip", "metrics.hip", "meters.hip", "optim.hip", "ingest.hip", "clipstore.hip", "panels.hip", "winograd.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_p16.hip", "layernorm.hip", "norm_act.hip", "dwconv.hip", "attn.hip", "attn_mfma.hip", "attn16.hip", "elementwise.hip", "conv7.hip", "losses.hip", "recon_loss.hip", "gan_loss.hip", "metrics.hip", "meters.hip", "optim.hip", "tensor_stats.hip", "ingest.hip", "clipstore.hip", "panels.hip", "winograd.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-ffp-contract=fast", "-fno-slp-vectorize",
          "-Wno-unused-result"]
 
@@ -45,7 +45,7 @@ def _compile(src, force):
             os.path.join(HERE, "..", "include", "vptr_hip_optim.h"), os.path.join(HERE, "..", "include", "vptr_hip_convffn.h"),
             os.path.join(HERE, "..", "include", "vptr_hip_accum.h"), os.path.join(HERE, "..", "include", "vptr_hip_loss.h"),
             os.path.join(HERE, "..", "include", "vptr_hip_gan.h"), os.path.join(HERE, "..", "include", "vptr_hip_groups.h"),
-            os.path.join(HERE, "..", "include", "vptr_hip_data.h")]
+            os.path.join(HERE, "..", "include", "vptr_hip_data.h"), os.path.join(HERE, "..", "include", "vptr_hip_diag.h")]
     dig = _digest(deps)
     if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig:
         return obj, False

@@ -6,7 +6,7 @@ rows = (n, t, h, w) flattened -- the reference's window partition and (T, N*HW, 
 
 Split by concern (round 6): core (configuration, seeds, raw GEMM, P16 format) / planes (weight-plane stores) / wgrad (launch planning of the
 deferred grouped weight gradients) / grads (gradient destinations: slabs, arena, autograd hand-off) / linear / norm / attention / convffn /
-layout / conv / losses / metrics / ingest / clipstore / panels (operator wrappers).  `vptr_amd.ops.<name>` keeps resolving every name the single module had.
+layout / conv / losses / metrics / ingest / clipstore / panels / diag (operator wrappers).  `vptr_amd.ops.<name>` keeps resolving every name the single module had.
 """
 from .core import (  # noqa: F401
     ACT_NONE, ACT_GELU, ACT_RELU, ACT_LRELU, PAD_MODES, _Config, config, set_deterministic, _direct_apply, _seed_state, _seed_scope,
@@ -68,5 +68,7 @@ from .clipstore import (  # noqa: F401
 from .panels import (  # noqa: F401
     PANELS_MAX_CLIPS, clip_panels, pad_indices, panel_shape,
 )
+from .diag import tensor_stats  # noqa: F401
+from . import diag  # noqa: F401,E402
 from . import core, planes, wgrad, grads, linear, norm, attention, convffn, layout, conv, losses, metrics, ingest, clipstore, panels  # noqa: F401,E402
 from .._lib import lib  # noqa: F401,E402  (tools patch ops.lib entry points)

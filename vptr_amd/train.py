@@ -38,8 +38,9 @@ import torch.nn.functional as F
 
 from . import ops
 from ._lib import check, lib, ptr, stream
+from .diagnostics import TensorStats, TensorStatsState
 from .model.criterion import GDL, GANLoss, L1Loss, MSELoss, temporal_weight_func
-from .optim import (S_GRAD_NORM, S_LR_NOW, S_SKIPPED_IN_A_ROW, S_SKIPPED_TOTAL, SCALE_KEY, STATE_KEY, W_APPLY_NOW, W_MICRO, GroupTable, LRSchedule, OptimControls,
+from .optim import (GS_LR, H_GRAD_SCALE, G_WORDS, S_GRAD_NORM, S_LR_NOW, S_SKIPPED_IN_A_ROW, S_SKIPPED_TOTAL, SCALE_KEY, STATE_KEY, W_APPLY_NOW, W_MICRO, GroupTable, LRSchedule, OptimControls,
                     group_map, resolve_param_groups)
 
 
@@ -263,15 +264,22 @@ class FlatAdamW:
     that no entry lists form group 0 with the defaults, the listed groups follow (optim.resolve_param_groups).  lr_scale 0 leaves a
     group's parameters bit for bit while its moments still move, as torch does with lr = 0; its gradient still counts in the clip norm.
     `set_group` rewrites a group between steps or replays, `group_lr(g)` is the rate it last used.  `step` then issues sumsq ->
-    prepare -> group scalars -> grouped update -> plane refresh: one kernel node more than the controlled step."""
+    prepare -> group scalars -> grouped update -> plane refresh: one kernel node more than the controlled step.
+
+    tensor_stats (a `diagnostics.TensorStats`), names (one string per trainable parameter in slab order; None: "param_<i>"): switches the
+    controls on as well and adds per-tensor statistics on the device (diagnostics.py, csrc/tensor_stats.hip): `step` issues one call of
+    two launches right behind the update -- so it sees the new p, m and v and this step's gradient, scaled by the record's grad_scale --
+    and ahead of the plane refresh.  `opt.tensor_stats` (a `diagnostics.TensorStatsState`) holds the `[S + 1, 8]` table, `view`s of its
+    words for `DeviceLossMeters`, `set_every` / `set_on_skip`, `report()` and `culprits()`.  Nothing of it enters `state_dict()`."""
 
     ctl = None   # optim.OptimControls when the controls are on
     ema = None   # the EMA slab (ema_decay=)
     groups = None   # optim.GroupTable (param_groups=)
+    tensor_stats = None   # diagnostics.TensorStatsState (tensor_stats=)
     _windowed = False
 
     def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, channel_last=(), schedule=None,
-                 skip_nonfinite=False, accum_steps=None, ema_decay=None, ema_warmup=True, param_groups=None):
+                 skip_nonfinite=False, accum_steps=None, ema_decay=None, ema_warmup=True, param_groups=None, tensor_stats=None, names=None):
         """channel_last: ids of [C, ...] parameters that the kernels consume channel-last (the (C,H,W) LayerNorm affines and
         the depthwise 3x3 weights of MlpDWBN): they are STORED channel-last in the slab and exposed as a permuted view of
         their usual shape, so no per-step transposes of the parameter or its gradient remain (AdamW is elementwise, the
@@ -279,6 +287,14 @@ class FlatAdamW:
         self.params = [p for p in params if p.requires_grad]
         if param_groups is not None:   # validated before any parameter is rebound to the slab
             self._group_of, group_specs = resolve_param_groups(self.params, param_groups)
+        if tensor_stats is not None:   # validated before any parameter is rebound to the slab, too
+            if not isinstance(tensor_stats, TensorStats):
+                raise ValueError("tensor_stats must be a vptr_amd.diagnostics.TensorStats, got %r" % (tensor_stats,))
+            from .diagnostics import check_names, plan
+            plan([p.numel() for p in self.params])
+            names = check_names(names, len(self.params))
+        elif names is not None:
+            raise ValueError("names= belongs to tensor_stats=")
         channel_last = set(channel_last)
         dev = self.params[0].device
         total = sum(p.numel() for p in self.params)
@@ -312,10 +328,17 @@ class FlatAdamW:
         self.step_dev = torch.zeros(1, device=dev, dtype=torch.float32)
         self.sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
         self._windowed = accum_steps is not None or ema_decay is not None
-        if schedule is not None or skip_nonfinite or self._windowed or param_groups is not None:
+        if schedule is not None or skip_nonfinite or self._windowed or param_groups is not None or tensor_stats is not None:
             self.ctl = OptimControls(dev, lr, betas, eps, weight_decay, max_grad_norm, schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup)
         if param_groups is not None:
             self.groups = GroupTable(dev, group_map(self._layout, self._group_of, total + pad), group_specs, weight_decay)
+        if tensor_stats is not None:
+            ts = self.tensor_stats = TensorStatsState(dev, [n for _, n, _ in self._layout], names, tensor_stats)
+            self._ts_scale = self.ctl.hyper[H_GRAD_SCALE:H_GRAD_SCALE + 1]
+            if self.groups is not None:   # where `report` finds each tensor's rate: the group table's words, or the one of the state record
+                ts.lr_dev, ts.lr_index = self.groups.gstate.view(-1, G_WORDS)[:, GS_LR], list(self._group_of)
+            else:
+                ts.lr_dev, ts.lr_index = self.ctl.state[S_LR_NOW:S_LR_NOW + 1], [0] * len(self.params)
         if ema_decay is not None:
             self.ema = self.flat.clone()
         if self._windowed:
@@ -668,6 +691,8 @@ class FlatAdamW:
                                  float(self.max_grad_norm or 0.0), float(grad_scale), stream()), "vptr_adamw")
         if prof is not None:
             ev[1].record()
+        if self.tensor_stats is not None:   # behind the update (the new p, m, v; this step's gradient), ahead of the plane refresh
+            self.tensor_stats.launch(self.flat, self.grad, self.m, self.v, self._ts_scale, self.ctl.state)
         if self.planes is not None:
             self.planes.refresh()
         if prof is not None:
@@ -693,8 +718,14 @@ class NARTrainer(_ReconMixin, _GanMixin):
 
     def __init__(self, enc, dec, transformer, batch_size, lr=1e-4, max_grad_norm=1.0, lam_pc=0.1, process_group=None,
                  bucket_mb=64, dec_weight_grads=True, disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False,
-                 accum_steps=None, ema_decay=None, ema_warmup=True, recon=None, gan_loss="torch", param_groups=None):
-        """param_groups: the parameter groups of the transformer's `FlatAdamW` (per-group lr_scale and weight_decay): a list of
+                 accum_steps=None, ema_decay=None, ema_warmup=True, recon=None, gan_loss="torch", param_groups=None, tensor_stats=None):
+        """tensor_stats: a `diagnostics.TensorStats` -- per-tensor gradient, weight and update statistics of the transformer's `FlatAdamW`
+        on the device, named as `transformer.named_parameters()` names them (`trainer.opt.tensor_stats`: table, `view`, `set_every`,
+        `report`, `culprits`).  It switches the device-resident controls on; a captured step gains two kernel nodes.  Data parallel: the
+        call runs behind the exchange, every rank computes the same table and no collective is added.  The discriminator's optimizer
+        (`disc=`) has none.
+
+        param_groups: the parameter groups of the transformer's `FlatAdamW` (per-group lr_scale and weight_decay): a list of
         {"params": [...], "lr_scale": 1.0, "weight_decay": None}, or a callable that takes the transformer and returns one, e.g.
         `optim.no_decay_groups`.  It switches the device-resident controls on; `trainer.opt.set_group(g, ...)` between steps or replays
         changes the next update, `trainer.opt.group_lr(g)` can go into `DeviceLossMeters`.  The discriminator's optimizer (`disc=`) stays
@@ -720,7 +751,7 @@ class NARTrainer(_ReconMixin, _GanMixin):
         skipped step leaves parameters, moments and step count untouched; it still refreshes the weight planes (from unchanged weights),
         still advances the dropout seed, and BatchNorm running statistics of the forward pass it belongs to have been updated already."""
         self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup, gan_loss, param_groups)
+                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup, gan_loss, param_groups, tensor_stats)
         self._init_recon(recon)
         # loss_name_list MSE / GDL(alpha=1) / BiPatchNCE(N, Tf, 8, 8, temperature 1.0) of train_NAR.py:176-179 run as the fused kernels of
         # csrc/losses.hip (ops.mse_gdl, ops.nce_loss): plain kernel launches only, so the step can live in a hipGraph (DESIGN.md section 6)
@@ -731,7 +762,7 @@ class NARTrainer(_ReconMixin, _GanMixin):
             self._bufsync = BufferSync(self.T, 0, process_group)   # DDP's per-forward broadcast of rank 0's BatchNorm statistics
 
     def _init_stage2(self, enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                     schedule, skip_nonfinite, accum_steps=None, ema_decay=None, ema_warmup=True, gan_loss="torch", param_groups=None):
+                     schedule, skip_nonfinite, accum_steps=None, ema_decay=None, ema_warmup=True, gan_loss="torch", param_groups=None, tensor_stats=None):
         """what both stage-2 recipes construct: frozen auto-encoder, optional adversarial branch, the transformer's flat-slab optimizer"""
         if disc is not None and (ema_decay is not None or (accum_steps is not None and accum_steps != 1)):
             raise ValueError("accum_steps > 1 / ema_decay are not available with the adversarial branch (disc=): the discriminator's "
@@ -754,7 +785,8 @@ class NARTrainer(_ReconMixin, _GanMixin):
         self.opt = FlatAdamW(self.T.parameters(), lr=lr, max_grad_norm=max_grad_norm, channel_last=_channel_last_ids(self.T),
                              schedule=schedule, skip_nonfinite=skip_nonfinite, accum_steps=accum_steps,
                              ema_decay=ema_decay, ema_warmup=ema_warmup,
-                             param_groups=param_groups(self.T) if callable(param_groups) else param_groups)
+                             param_groups=param_groups(self.T) if callable(param_groups) else param_groups, tensor_stats=tensor_stats,
+                             names=None if tensor_stats is None else [n for n, p in self.T.named_parameters() if p.requires_grad])
         self._bufsync = None
         self._graph = None
 
@@ -1389,12 +1421,12 @@ class FARTrainer(NARTrainer):
 
     def __init__(self, enc, dec, transformer, lr=1e-4, max_grad_norm=1.0, process_group=None, bucket_mb=64, dec_weight_grads=True,
                  disc=None, lam_gan=None, gan_mode="vanilla", schedule=None, skip_nonfinite=False, accum_steps=None, ema_decay=None,
-                 ema_warmup=True, recon=None, gan_loss="torch", param_groups=None):
-        """schedule / skip_nonfinite / accum_steps / ema_decay / ema_warmup / recon / gan_loss / param_groups: as in `NARTrainer`; the temporal
+                 ema_warmup=True, recon=None, gan_loss="torch", param_groups=None, tensor_stats=None):
+        """schedule / skip_nonfinite / accum_steps / ema_decay / ema_warmup / recon / gan_loss / param_groups / tensor_stats: as in `NARTrainer`; the temporal
         weights of a `ReconLoss` have Tp - 1 + Tf entries here, one per frame of cat(past[:, 1:], future)"""
         # no BufferSync: the FAR transformer has no BatchNorm (LayerNorm conv-FFNs), nothing to broadcast per forward
         self._init_stage2(enc, dec, transformer, lr, max_grad_norm, process_group, bucket_mb, dec_weight_grads, disc, lam_gan, gan_mode,
-                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup, gan_loss, param_groups)
+                          schedule, skip_nonfinite, accum_steps, ema_decay, ema_warmup, gan_loss, param_groups, tensor_stats)
         self._init_recon(recon)
 
     def _encode(self, past, future):
@@ -1426,11 +1458,12 @@ class AETrainer(_ReconMixin, _GanMixin):
     AdamW with weight_decay 0, so both optimizers are `FlatAdamW` slabs (no clipping in this stage)."""
 
     def __init__(self, enc, dec, disc, lr=2e-4, lam_gan=0.01, betas=(0.5, 0.999), gan_mode="vanilla", schedule=None, skip_nonfinite=False,
-                 accum_steps=None, ema_decay=None, recon=None, gan_loss="torch", param_groups=None):
+                 accum_steps=None, ema_decay=None, recon=None, gan_loss="torch", param_groups=None, tensor_stats=None):
         """recon: a `ReconLoss` with `point` and `gdl_alpha` only (the stage-1 loss has no time axis to weight: temporal weights raise
         ValueError); `step` and `eval_step` then also return "AE_L1".
 
         param_groups: not available here (ValueError): stage 1 is plain Adam without weight decay on both optimizers.
+        tensor_stats: not available here either (ValueError): the statistics belong to the stage-2 trainers' transformer optimizer.
 
         gan_loss: "torch" or "fused", as in `NARTrainer`: the discriminator update's two losses and 0.5 * lam_gan * (their sum) in one
         `ops.gan_loss_pair`, the generator's term in one `ops.gan_loss`.
@@ -1446,6 +1479,9 @@ class AETrainer(_ReconMixin, _GanMixin):
         if param_groups is not None:
             raise ValueError("param_groups are not available for the stage-1 step (Adam without weight decay on Enc + Dec and on the "
                              "discriminator); they belong to the stage-2 trainers' transformer optimizer")
+        if tensor_stats is not None:
+            raise ValueError("tensor_stats are not available for the stage-1 step (two optimizers that alternate inside one iteration); "
+                             "they belong to the stage-2 trainers' transformer optimizer")
         self._init_recon(recon)
         self._init_gan_loss(gan_loss, gan_mode)
         if recon is not None and recon.has_weights:
