@@ -183,6 +183,12 @@ DATA_SIGNATURES = {
 DIAG_SIGNATURES = {
     "vptr_tensor_stats": [P, P, P, P, P, P, I, P, P, P, P, P, L, I, P],
 }
+# KV-cached decoding at a device-held position (csrc/attn.hip), declared in include/vptr_hip_decode.h (additive as well)
+DECODE_SIGNATURES = {
+    "vptr_decode_begin": [P, P, P, I, I, P],
+    "vptr_tattn_step_pos": [P, P, P, P, P, P, P, I, I, I, I, I, P],
+    "vptr_decode_advance": [P, P],
+}
 
 
 def _load():
@@ -191,7 +197,7 @@ def _load():
             "vptr_amd: %s is missing. Build it with `python -m vptr_amd.build` (needs hipcc, gfx950). "
             "There is no CPU / PyTorch fallback for the VPTR hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(GAN_SIGNATURES.items()) + list(GROUP_SIGNATURES.items()) + list(DATA_SIGNATURES.items()) + list(DIAG_SIGNATURES.items()):
+    for name, argt in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CONVFFN_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(GAN_SIGNATURES.items()) + list(GROUP_SIGNATURES.items()) + list(DATA_SIGNATURES.items()) + list(DIAG_SIGNATURES.items()) + list(DECODE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.argtypes = argt
         fn.restype = c_int

@@ -45,7 +45,8 @@ def _compile(src, force):
             os.path.join(HERE, "..", "include", "vptr_hip_optim.h"), os.path.join(HERE, "..", "include", "vptr_hip_convffn.h"),
             os.path.join(HERE, "..", "include", "vptr_hip_accum.h"), os.path.join(HERE, "..", "include", "vptr_hip_loss.h"),
             os.path.join(HERE, "..", "include", "vptr_hip_gan.h"), os.path.join(HERE, "..", "include", "vptr_hip_groups.h"),
-            os.path.join(HERE, "..", "include", "vptr_hip_data.h"), os.path.join(HERE, "..", "include", "vptr_hip_diag.h")]
+            os.path.join(HERE, "..", "include", "vptr_hip_data.h"), os.path.join(HERE, "..", "include", "vptr_hip_diag.h"),
+            os.path.join(HERE, "..", "include", "vptr_hip_decode.h")]
     dig = _digest(deps)
     if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig:
         return obj, False

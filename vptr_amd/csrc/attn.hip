@@ -5,6 +5,7 @@
 #include <initializer_list>
 
 #include "attn_mfma.h"
+#include "../../include/vptr_hip_decode.h"
 
 #define ATT_MAXL 64   // max tokens per window (ws <= 8)
 #define ATT_MAXT 64   // max time steps
@@ -896,6 +897,122 @@ extern "C" int vptr_tattn_step(const float* q, const float* kcache, const float*
     tattn_step_kernel<2><<<dim3((unsigned)grid), 64, 0, (hipStream_t)stream>>>(q, kcache, vcache, o, rows, Tk, C, nh, p16);
   else
     tattn_step_kernel<1><<<dim3((unsigned)grid), 64, 0, (hipStream_t)stream>>>(q, kcache, vcache, o, rows, Tk, C, nh, p16);
+  VPTR_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// the same step at a DEVICE-HELD position (include/vptr_hip_decode.h): t = rec[POS] is one wave-uniform load, so one captured launch
+// serves every frame.  Frame t's keys / values come from the staging buffers kn / vn [rows, C] (the projection GEMM's fixed outputs):
+// the wave stores its head slice of them into slot t of the caches and takes iteration j = t of both loops from the registers it
+// stored from -- no wave reads slot t.  Loops 0 .. t-1 and every expression are tattn_step_kernel's (bit-identical o).
+// ------------------------------------------------------------------------------------------------------------
+static_assert(VPTR_DECODE_MAXT == ATT_MAXT, "the position kernels share the step kernel's key limit");
+
+template <int V>
+__global__ __launch_bounds__(64) void tattn_step_pos_kernel(const float* __restrict__ q, const float* __restrict__ kn,
+                                                            const float* __restrict__ vn, float* __restrict__ kc, float* __restrict__ vc,
+                                                            float* __restrict__ o, const int32_t* __restrict__ rec, int rows, int Tcap,
+                                                            int C, int nh, int p16) {
+  using Vec = StepVec<V>;
+  const int t = rec[VPTR_DECODE_POS];
+  if (t < 0 || t >= Tcap || t >= ATT_MAXT) return;   // uniform over the grid: nothing is stored
+  const int h = (blockIdx.x >> 3) % nh, r = (blockIdx.x / (8 * nh)) * 8 + (blockIdx.x & 7), lane = threadIdx.x;
+  if (r >= rows) return;
+  const int hd = C / nh, n = hd / V, nch = (n + 63) >> 6;
+  const int64_t slab = (int64_t)rows * C, base = (int64_t)r * C + h * hd;
+  const bool in0 = lane < n;
+  const int e0 = min(lane, n - 1) * V;
+  const Vec q0 = Vec::ld(q + base + e0);
+  float s = -INFINITY;
+#pragma unroll 4
+  for (int j = 0; j < t; ++j) {
+    const float* kr = kc + j * slab + base;
+    float part = in0 ? q0.dot(Vec::ld(kr + e0)) : 0.f;
+    for (int c = 1; c < nch; ++c) {
+      const int i = lane + c * 64, e = min(i, n - 1) * V;
+      const float d = Vec::ld(q + base + e).dot(Vec::ld(kr + e));
+      part += i < n ? d : 0.f;
+    }
+    const float sj = wave_sum(part);
+    s = lane == j ? sj : s;
+  }
+  {   // j = t: the new frame's key, appended on the way
+    const float* kr = kn + base;
+    float* ks = kc + t * slab;
+    const Vec k0 = Vec::ld(kr + e0);
+    if (in0) k0.st(ks, base + e0, 0);
+    float part = in0 ? q0.dot(k0) : 0.f;
+    for (int c = 1; c < nch; ++c) {
+      const int i = lane + c * 64, e = min(i, n - 1) * V;
+      const Vec kk = Vec::ld(kr + e);
+      if (i < n) kk.st(ks, base + e, 0);
+      const float d = Vec::ld(q + base + e).dot(kk);
+      part += i < n ? d : 0.f;
+    }
+    const float sj = wave_sum(part);
+    s = lane == t ? sj : s;
+  }
+  const float m = wave_max(s);
+  const float ex = lane <= t ? __expf(s - m) : 0.f;
+  const float pr = ex / wave_sum(ex);
+  for (int c = 0; c < nch; ++c) {
+    const int i = lane + c * 64, e = min(i, n - 1) * V;
+    Vec acc = {};
+#pragma unroll 4
+    for (int j = 0; j < t; ++j) acc.axpy(__shfl(pr, j, 64), Vec::ld(vc + j * slab + base + e));
+    const Vec vv = Vec::ld(vn + base + e);
+    if (i < n) vv.st(vc + t * slab, base + e, 0);
+    acc.axpy(__shfl(pr, t, 64), vv);
+    if (i < n) acc.st(o, base + e, p16);
+  }
+}
+
+extern "C" int vptr_tattn_step_pos(const float* q, const float* knew, const float* vnew, float* kcache, float* vcache, float* o,
+                                   const int32_t* rec, int rows, int Tcap, int C, int nh, int p16, vptr_stream_t stream) {
+  VPTR_CHECK(q && knew && vnew && kcache && vcache && o && rec, "tattn_step_pos: NULL pointer");
+  VPTR_CHECK(rows > 0 && Tcap > 0 && C > 0 && nh > 0, "tattn_step_pos: bad arguments");
+  VPTR_CHECK(C % nh == 0, "tattn_step_pos: embed_dim must be divisible by num_heads");
+  if (p16) VPTR_CHECK(C % 16 == 0, "tattn_step_pos: P16 outputs need C %% 16 == 0 (got %d)", C);
+  const int64_t grid = (int64_t)cdiv(rows, 8) * 8 * nh;
+  VPTR_CHECK(grid <= 0x7fffffff, "tattn_step_pos: too many (row, head) pairs");
+  if ((C / nh) % 2 == 0)
+    tattn_step_pos_kernel<2><<<dim3((unsigned)grid), 64, 0, (hipStream_t)stream>>>(q, knew, vnew, kcache, vcache, o, rec, rows, Tcap, C, nh, p16);
+  else
+    tattn_step_pos_kernel<1><<<dim3((unsigned)grid), 64, 0, (hipStream_t)stream>>>(q, knew, vnew, kcache, vcache, o, rec, rows, Tcap, C, nh, p16);
+  VPTR_LAUNCH_CHECK();
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void decode_begin_kernel(const int32_t* __restrict__ rec, const float* __restrict__ tpos,
+                                                           float* __restrict__ cur, int Tmax, int C) {
+  const int t = rec[VPTR_DECODE_POS], cap = min(rec[VPTR_DECODE_TCAP], Tmax);
+  if (t < 0 || t >= cap) return;
+  for (int c = threadIdx.x; c < C; c += 256) cur[c] = tpos[(int64_t)t * C + c];
+}
+
+extern "C" int vptr_decode_begin(const int32_t* rec, const float* tpos, float* tpos_cur, int Tmax, int C, vptr_stream_t stream) {
+  VPTR_CHECK(rec && tpos && tpos_cur, "decode_begin: NULL pointer");
+  VPTR_CHECK(Tmax > 0 && C > 0, "decode_begin: bad arguments (Tmax = %d, C = %d)", Tmax, C);
+  decode_begin_kernel<<<dim3(1), 256, 0, (hipStream_t)stream>>>(rec, tpos, tpos_cur, Tmax, C);
+  VPTR_LAUNCH_CHECK();
+  return 0;
+}
+
+__global__ __launch_bounds__(64) void decode_advance_kernel(int32_t* rec) {
+  if (threadIdx.x != 0) return;
+  const int t = rec[VPTR_DECODE_POS];
+  if (t >= 0 && t < rec[VPTR_DECODE_TCAP]) {
+    rec[VPTR_DECODE_POS] = t + 1;
+    rec[VPTR_DECODE_STEPS] += 1;
+  } else {
+    rec[VPTR_DECODE_OVERFLOW] += 1;
+  }
+}
+
+extern "C" int vptr_decode_advance(int32_t* rec, vptr_stream_t stream) {
+  VPTR_CHECK(rec, "decode_advance: NULL pointer");
+  decode_advance_kernel<<<dim3(1), 64, 0, (hipStream_t)stream>>>(rec);
   VPTR_LAUNCH_CHECK();
   return 0;
 }

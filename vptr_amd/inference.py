@@ -19,8 +19,12 @@ The reference defines them in Test_VPTR.ipynb cell 5 and train_FAR.py:103-125; t
 Everything runs under no_grad through the same HIP kernels as training (eval mode: dropout / DropPath off).
 `far_rollout(kv_cache=True)` feeds the transformer one new frame per step against cached temporal-attention keys / values
 (`VPTRFormerFAR.forward_cached`, the `vptr_tattn_step` kernel) instead of re-running it over the whole window.
+`far_rollout(kv_cache=True, graph=True)` / `CachedDecoder` replay ONE captured hipGraph per cached step: the frame index lives in a
+device record (include/vptr_hip_decode.h), so the same graph serves every frame of every rollout at a batch size.
 """
 import torch
+
+from . import ops
 
 
 @torch.no_grad()
@@ -67,7 +71,7 @@ def nar_bair_2_to_28(enc, dec, T, past):
 
 
 @torch.no_grad()
-def far_rollout(enc, dec, T, past, num_pred, mode="train", kv_cache=False):
+def far_rollout(enc, dec, T, past, num_pred, mode="train", kv_cache=False, graph=False):
     """mode 'RIP' / 'RIL': past (N,Tp,C,H,W) -> predicted future frames (N,num_pred,C,H,W).
     mode 'train': -> (pred_past_frames (N,Tp-1,...), pred_future_frames (N,num_pred,...)) exactly as FAR_show_sample's test phase.
 
@@ -77,7 +81,18 @@ def far_rollout(enc, dec, T, past, num_pred, mode="train", kv_cache=False):
     passes; the two paths run different attention kernels and agree to rounding, not bitwise).  'train': the per-frame outputs are
     collected and decoded once -- the tensor the last full pass returns.  'RIP' / 'RIL': cached while the window only grows; from
     the first step at which the window slides, every position (hence every frame's activations) changes and nothing in the cache is
-    reusable, so the rest of the rollout recomputes the slid window as kv_cache=False does."""
+    reusable, so the rest of the rollout recomputes the slid window as kv_cache=False does.
+
+    graph=True (with kv_cache=True only, else ValueError): the cached steps are replays of one captured hipGraph (`CachedDecoder`, built
+    and captured by this call); graph=<a CachedDecoder> reuses one that was built for these modules, this batch size and this mode."""
+    if graph is not False and graph is not None:
+        if not kv_cache:
+            raise ValueError("far_rollout: graph=True replays the KV-cached step; it needs kv_cache=True")
+        T.eval()
+        d = graph if isinstance(graph, CachedDecoder) else CachedDecoder(enc, dec, T, past.shape[0], mode)
+        if (d.enc, d.dec, d.T, d.mode) != (enc, dec, T, mode):
+            raise ValueError("far_rollout: the CachedDecoder was built for other modules or another mode")
+        return d.rollout(past, num_pred)
     T.eval()
     past_feats = enc(past)
     if kv_cache:
@@ -138,3 +153,178 @@ def _far_rollout_cached(enc, dec, T, past_feats, num_pred, mode):
         frames.append(frame)
         newest = enc(frame) if mode == "RIP" else last
     return torch.cat(frames, dim=1)
+
+
+def _graph_degrees(g):
+    """(nodes, nodes with more than one successor or predecessor) of a torch.cuda.CUDAGraph captured with keep_graph=True"""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    graph = ctypes.c_void_p(int(g.raw_cuda_graph()))
+    n = ctypes.c_size_t(0)
+    if hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) != 0:
+        raise RuntimeError("hipGraphGetNodes failed")
+    e = ctypes.c_size_t(0)
+    if hip.hipGraphGetEdges(graph, None, None, ctypes.byref(e)) != 0:
+        raise RuntimeError("hipGraphGetEdges failed")
+    src, dst = (ctypes.c_void_p * max(e.value, 1))(), (ctypes.c_void_p * max(e.value, 1))()
+    if e.value and hip.hipGraphGetEdges(graph, src, dst, ctypes.byref(e)) != 0:
+        raise RuntimeError("hipGraphGetEdges failed")
+    out, inn = {}, {}
+    for i in range(e.value):
+        out[src[i]] = out.get(src[i], 0) + 1
+        inn[dst[i]] = inn.get(dst[i], 0) + 1
+    return n.value, sum(1 for v in out.values() if v > 1) + sum(1 for v in inn.values() if v > 1)
+
+
+class CachedDecoder:
+    """KV-cached FAR rollouts at batch size N whose cached steps are replays of ONE captured hipGraph.
+
+    Owns a `FARCache(device_pos=True)` (the frame index is a device record the kernels read by address, so nothing in the step depends
+    on a host value), the static feature buffer `x` the step reads and overwrites, and for 'RIP' the static frame buffer.  The graph:
+      'RIL'   x <- T.forward_cached(x)                 the features are collected with one eager copy per step, decoded once at the end
+      'RIP'   last = T.forward_cached(x); frame <- dec(last); x <- enc(frame)
+      'train' x <- T.forward_cached(enc(dec(x)))       from the second step on; the first step takes the raw prediction and runs eagerly
+    It is captured on one stream at the first `rollout` (the procedure of the trainers' `_capture`: eager warm-up passes on a side
+    stream, reserved staging, the node census -- kernel, memcpy and empty nodes only, a memset node raises) and replayed ever after:
+    `captures` counts the captures.  The graph reads the weights by address (the trainers' parameter slab and its P16 images, which the
+    eager prefill of every rollout refreshes), so it follows optimizer steps and EMA swaps; the auto-encoder must stay as it was at
+    the capture (it is frozen in stage 2).  `rollout` is `far_rollout(kv_cache=True)`'s loop: eager prefill, replays while the window
+    grows, today's un-cached recomputation once it slides."""
+
+    MODES = ("train", "RIP", "RIL")
+
+    def __init__(self, enc, dec, T, N, mode, warmup=2):
+        if mode not in self.MODES:
+            raise ValueError("far_rollout: mode must be 'train', 'RIP' or 'RIL'")
+        if T.training or enc.training or dec.training:
+            raise ValueError("CachedDecoder: the captured step is eval-only (call .eval() on the encoder, the decoder and the transformer)")
+        if isinstance(N, bool) or int(N) < 1:
+            raise ValueError("CachedDecoder: N must be a batch size >= 1")
+        self.enc, self.dec, self.T, self.N, self.mode, self.warmup = enc, dec, T, int(N), mode, max(int(warmup), 1)
+        self.cache = T.init_cache(self.N, device_pos=True)
+        tr = T.transformer
+        self.x = torch.zeros((self.N, 1, tr.in_C, tr.H, tr.W), device=self.cache.pos.device, dtype=torch.float32)
+        self.frame = None
+        self.graph, self.graph_nodes, self.graph_branches, self.captures, self.capture_seconds = None, None, None, 0, None
+        self._scratch = None
+
+    # -- the step -------------------------------------------------------------------------------------------------------------------
+    def _body(self):
+        T, x = self.T, self.x
+        if self.mode == "RIL":
+            x.copy_(T.forward_cached(x, self.cache))
+        elif self.mode == "RIP":
+            frame = self.dec(T.forward_cached(x, self.cache))
+            if self.frame is None:
+                self.frame = torch.empty_like(frame)
+            self.frame.copy_(frame)
+            x.copy_(self.enc(frame))
+        else:
+            x.copy_(T.forward_cached(self.enc(self.dec(x)), self.cache))
+
+    def _capture(self):
+        import time
+        from .train import graph_node_census
+        t0 = time.perf_counter()
+        cache = self.cache
+        keep = self.x.clone()
+
+        def warm():
+            cache.reset()
+            self._body()
+
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(self.warmup - 1):
+                warm()
+            ops._upload_stats.update(count=0, max_bytes=0)
+            warm()
+        torch.cuda.current_stream().wait_stream(s)
+        ops.reserve_graph_staging(count=ops._upload_stats["count"] + 4, nbytes=max(1 << 16, 2 * ops._upload_stats["max_bytes"]))
+        cache.reset()
+        g = torch.cuda.CUDAGraph(keep_graph=True)
+        with torch.cuda.graph(g):
+            self._body()
+        cache.reset()
+        self.x.copy_(keep)
+        nodes = graph_node_census(g)
+        self.graph_nodes = nodes
+        bad = {k: v for k, v in nodes.items() if k not in ("kernel", "memcpy", "empty")}
+        if bad:
+            g.reset()
+            raise RuntimeError("captured decoding step holds node types that are not replay-safe on this HIP runtime: %s (all nodes: %s)" % (bad, nodes))
+        self.graph_branches = _graph_degrees(g)[1]
+        if self.graph_branches:
+            g.reset()
+            raise RuntimeError("captured decoding step has %d nodes with parallel branches; it must be one chain" % self.graph_branches)
+        g.instantiate()
+        # shape-keyed scratch of the frozen auto-encoder that the graph reads and writes by address (NARTrainer._module_scratch)
+        self._scratch = [getattr(m, a) for mod in (self.enc, self.dec) for m in mod.modules() for a in ("_plane_bufs", "_head_bufs", "_wino_bufs")
+                         if getattr(m, a, None) is not None]
+        self.graph = g
+        self.captures += 1
+        torch.cuda.synchronize()
+        self.capture_seconds = time.perf_counter() - t0
+
+    def step(self):
+        """one cached step on `x` (and `frame`): a replay.  ValueError on the host, before the replay, if it would pass the capacity."""
+        cache = self.cache
+        if cache.len + 1 > cache.Tcap:
+            raise ValueError("forward_cached: %d cached + 1 new frames exceed the cache's %d" % (cache.len, cache.Tcap))
+        self.graph.replay()
+        cache.len += 1
+
+    # -- the rollout ----------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def rollout(self, past, num_pred):
+        """far_rollout(enc, dec, T, past, num_pred, mode, kv_cache=True) with replayed steps"""
+        enc, dec, T, cache, x, mode = self.enc, self.dec, self.T, self.cache, self.x, self.mode
+        if past.dim() != 5 or past.shape[0] != self.N:
+            raise ValueError("CachedDecoder: built for batches of %d samples, got a past of shape %s" % (self.N, tuple(past.shape)))
+        if T.training or enc.training or dec.training:
+            raise ValueError("CachedDecoder: the captured step is eval-only")
+        if self.graph is None:
+            self._capture()
+        past_feats = enc(past)
+        cache.reset()
+        out = T.forward_cached(past_feats, cache)      # prefill (eager); ends with POS = Tp
+        x.copy_(out[:, -1:])
+        if mode == "train":
+            outs = [out]
+            for i in range(num_pred - 1):
+                if i == 0:
+                    x.copy_(T.forward_cached(x, cache))   # the raw prediction: no Dec -> Enc round trip
+                else:
+                    self.step()
+                outs.append(x.clone())
+            frames = dec(torch.cat(outs, dim=1))
+            return frames[:, :-num_pred], frames[:, -num_pred:]
+        horizon = T.num_future_frames
+        frames = [dec(x)]
+        window = past_feats
+        newest = x.clone()
+        lasts = []
+        slid = False
+        for i in range(1, num_pred):
+            window = torch.cat([window, newest], dim=1)
+            if i > 1 and i >= horizon:
+                window = window[:, 1:]
+                slid = True
+            if slid:
+                last = T(window)[:, -1:]
+                frame = dec(last)
+                frames.append(frame)
+                newest = enc(frame) if mode == "RIP" else last
+                continue
+            self.step()
+            newest = x.clone()
+            if mode == "RIP":
+                frames.append(self.frame.clone())
+            else:
+                lasts.append(newest)
+        if mode == "RIL" and lasts:                    # ONE decoder pass over the replayed steps' features
+            n = len(lasts)
+            dl = dec(torch.cat(lasts, dim=1))
+            frames[1:1] = [dl[:, j:j + 1] for j in range(n)]
+        return torch.cat(frames, dim=1)

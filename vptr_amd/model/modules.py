@@ -168,12 +168,13 @@ class VPTRFormerFAR(nn.Module):
         ops.ensure_module_planes(self)
         return self.transformer(input_feats, self.lw_pos, self.temporal_pos)
 
-    def init_cache(self, N, device=None):
+    def init_cache(self, N, device=None, device_pos=False):
         """An empty key / value cache (vidhrformer.FARCache) for forward_cached on batches of N samples: per layer two
         [Tcap, N*encH*encW, d_model] fp32 tensors, Tcap = num_past_frames + num_future_frames (the length of temporal_pos).  The cache
-        owns num_encoder_layers * 2 * Tcap * N*encH*encW * d_model * 4 bytes -- 1.6 GB for the BAIR model (12 layers, 30 frames) at batch 16."""
+        owns num_encoder_layers * 2 * Tcap * N*encH*encW * d_model * 4 bytes -- 1.6 GB for the BAIR model (12 layers, 30 frames) at batch 16.
+        device_pos=True: the position is also kept in a device record, so that a step can be captured once (FARCache)."""
         device = self.temporal_pos.device if device is None else torch.device(device)
-        return self.transformer.init_cache(int(N), self.temporal_pos.shape[0], device)
+        return self.transformer.init_cache(int(N), self.temporal_pos.shape[0], device, device_pos=device_pos)
 
     def forward_cached(self, feats, cache):
         """KV-cached inference: feats (N,Tn,C,H,W) are appended at positions cache.len .. cache.len+Tn-1 and their outputs (N,Tn,C,H,W)

@@ -357,12 +357,13 @@ class VidHRFormerBlockEnc(nn.Module):
         h = ops.linear(u, self.linear1.weight, self.linear1.bias, act=ops.ACT_GELU, dropout_p=p, site=s + 5, x_p16=P, out_p16=P)
         return ops.linear(h, self.linear2.weight, self.linear2.bias, residual=xr, dropout_p=p, site=s + 6, x_p16=P)
 
-    def step_tokens(self, x, g1, lw_pos, tpos_t, kc, vc, t):
+    def step_tokens(self, x, g1, lw_pos, tpos_t, kc, vc, t, pos=None, staging=None):
         """One KV-cached decoding step (far=True, eval mode, no grad): x [N*H*W, C] are the tokens of frame t alone, g1 = Geom(N, 1, H, W),
         tpos_t = temporal_pos[t:t+1], kc / vc [Tcap, N*H*W, C] this layer's time-major key / value cache holding frames 0 .. t-1.
         Every sub-layer but the causal temporal attention is frame-local in eval mode, so the sequence is forward_tokens' on one frame;
         the temporal attention projects frame t into slot t of the cache and attends over slots 0 .. t (ops.proj_temporal_attention_step).
-        Returns frame t's tokens exactly as row block t of forward_tokens over frames 0 .. t."""
+        Returns frame t's tokens exactly as row block t of forward_tokens over frames 0 .. t.
+        pos / staging: the device-held position of a `FARCache(device_pos=True)` (tpos_t is then its `tpos_cur` row, t unused)."""
         if self.training or not self.far:
             raise RuntimeError("step_tokens: KV-cached decoding needs a far=True block in eval mode")
         HW = g1.H * g1.W
@@ -378,7 +379,7 @@ class VidHRFormerBlockEnc(nn.Module):
         mha = self.temporal_MHSA
         C, w, b = mha.embed_dim, mha.in_proj_weight, mha.in_proj_bias
         o = ops.proj_temporal_attention_step(uq, u, w[:C], b[:C], w[C:2 * C], b[C:2 * C], w[2 * C:], b[2 * C:], kc, vc, t, mha.num_heads,
-                                             x_p16=P, o_p16=P)
+                                             x_p16=P, o_p16=P, pos=pos, staging=staging)
         x = ops.linear(o, mha.out_proj.weight, mha.out_proj.bias, residual=xr, x_p16=P)
         u, xr = ops.layernorm(x, self.norm4.weight, self.norm4.bias, eps=self.norm4.eps, passthrough=True, out_p16=P)
         if P and ops.config.fused_mlp:
@@ -402,10 +403,11 @@ class VidHRFormerEncoder(nn.Module):
             x = ops.layernorm(x, self.norm.weight, self.norm.bias, eps=self.norm.eps)
         return x
 
-    def step_tokens(self, x, g1, lw_pos, tpos_t, ks, vs, t):
+    def step_tokens(self, x, g1, lw_pos, tpos_t, ks, vs, t, pos=None, staging=None):
         """one KV-cached frame through every layer (VidHRFormerBlockEnc.step_tokens); ks / vs: the per-layer caches"""
         for layer, kc, vc in zip(self.layers, ks, vs):
-            x = layer.step_tokens(x, g1, lw_pos, tpos_t, kc, vc, t)
+            x = layer.step_tokens(x, g1, lw_pos, tpos_t, kc, vc, t) if pos is None else \
+                layer.step_tokens(x, g1, lw_pos, tpos_t, kc, vc, t, pos, staging)
         if self.norm is not None:
             x = ops.layernorm(x, self.norm.weight, self.norm.bias, eps=self.norm.eps)
         return x
@@ -618,8 +620,8 @@ class VidHRFormerFAR(nn.Module):
             _dp_plan[0] = None
         return out
 
-    def init_cache(self, N, Tcap, device):
-        return FARCache(self.num_encoder_layer, Tcap, N, self.H, self.W, self.embed_dim, device)
+    def init_cache(self, N, Tcap, device, device_pos=False):
+        return FARCache(self.num_encoder_layer, Tcap, N, self.H, self.W, self.embed_dim, device, device_pos=device_pos)
 
     @torch.no_grad()
     def forward_cached(self, feats, local_window_pos_embed, temporal_pos_embed, cache):
@@ -627,7 +629,11 @@ class VidHRFormerFAR(nn.Module):
         frames of forward() over the whole sequence so far (every sub-layer but the causal temporal attention is frame-local in eval
         mode, so a frame's activations depend on earlier frames through the cached keys / values alone).  Several frames at once only
         into an empty cache (prefill: the ordinary causal pass, whose projected keys / values are copied into the cache, one strided
-        copy per layer and tensor); afterwards one frame per call (VidHRFormerBlockEnc.step_tokens)."""
+        copy per layer and tensor); afterwards one frame per call (VidHRFormerBlockEnc.step_tokens).
+
+        On a `FARCache(device_pos=True)` a single-frame step reads its position from the cache's device record: vptr_decode_begin,
+        the layers on `tpos_cur` and the record, vptr_decode_advance -- the same launches for every frame, eager or captured.  The
+        capacity check is made on the host mirror `cache.len`, before any launch."""
         if self.training:
             raise ValueError("forward_cached: KV-cached decoding is eval-only (dropout / DropPath must be off)")
         if feats.dim() != 5:
@@ -651,8 +657,22 @@ class VidHRFormerFAR(nn.Module):
                 return hook
             out = self.forward(feats, local_window_pos_embed, temporal_pos_embed, [export(kc, vc) for kc, vc in zip(cache.k, cache.v)])
             cache.len = Tn
+            if cache.pos is not None:
+                cache.put_pos(Tn)
             return out
         t = cache.len
+        if cache.pos is not None:
+            if temporal_pos_embed.dtype != torch.float32 or not temporal_pos_embed.is_contiguous():
+                raise ValueError("forward_cached: a device-held position needs a contiguous fp32 temporal position table")
+            with ops.zero_arena(_ln_ffn_stats_floats(self.encoder, N), feats.device):
+                ops.decode_begin(cache.pos, temporal_pos_embed, cache.tpos_cur)
+                x = ops.nchw_to_tokens(feats.reshape(N, C, H, W))
+                x = self.encoder.step_tokens(x, Geom(N, 1, H, W), local_window_pos_embed, cache.tpos_cur.view(1, C), cache.k, cache.v, None,
+                                             cache.pos, cache.staging)
+                out = ops.tokens_to_nchw(x, N, C, H, W, relu=True).reshape(N, 1, C, H, W)
+                ops.decode_advance(cache.pos)
+            cache.len = t + 1
+            return out
         with ops.zero_arena(_ln_ffn_stats_floats(self.encoder, N), feats.device):
             x = ops.nchw_to_tokens(feats.reshape(N, C, H, W))
             x = self.encoder.step_tokens(x, Geom(N, 1, H, W), local_window_pos_embed, temporal_pos_embed[t:t + 1], cache.k, cache.v, t)
@@ -665,15 +685,52 @@ class FARCache:
     """Key / value cache of VidHRFormerFAR.forward_cached: per layer the temporal attention's projected keys and values of every frame
     fed so far, `k[l]`, `v[l]`: [Tcap, N*H*W, C] fp32, TIME-MAJOR (frame t is one contiguous [N*H*W, C] slab, which a decoding step's
     projection GEMM writes in place); `len` frames are valid.  Owns layers * 2 * Tcap * N*H*W * C * 4 bytes (12 layers, 30 frames,
-    batch 16 of 8x8 x 528 features: 1.6 GB)."""
+    batch 16 of 8x8 x 528 features: 1.6 GB).
 
-    def __init__(self, layers, Tcap, N, H, W, C, device):
+    device_pos=True: the position also lives on the device (include/vptr_hip_decode.h), so that a single-frame step issues the same
+    launches for every frame and one captured graph serves a whole rollout.  The cache then owns the int32 record `pos` (POS, TCAP,
+    OVERFLOW, STEPS), `tpos_cur` [C] (the temporal-position row of the current frame) and `staging` = (k, v) [N*H*W, C], the projection
+    outputs every layer shares.  `len` stays the host's mirror of POS: it is deterministic (one per step) and is what the capacity
+    check reads; the device's OVERFLOW word is the backstop, read by `check()`.  The host writes POS with fill kernels only."""
+
+    pos = tpos_cur = staging = None
+
+    def __init__(self, layers, Tcap, N, H, W, C, device, device_pos=False):
         self.Tcap, self.N, self.H, self.W, self.C, self.len = int(Tcap), int(N), int(H), int(W), int(C), 0
+        if device_pos:
+            if self.Tcap > ops.DECODE_MAXT:
+                raise ValueError("FARCache: a device-held position serves at most %d frames (got %d)" % (ops.DECODE_MAXT, self.Tcap))
+            self.pos = torch.zeros(ops.DECODE_WORDS, device=device, dtype=torch.int32)
+            self.pos[ops.DECODE_TCAP:ops.DECODE_TCAP + 1].fill_(self.Tcap)
+            self.tpos_cur = torch.zeros(C, device=device, dtype=torch.float32)
+            self.staging = (torch.empty((N * H * W, C), device=device, dtype=torch.float32),
+                            torch.empty((N * H * W, C), device=device, dtype=torch.float32))
         self.k = [torch.empty((self.Tcap, N * H * W, C), device=device, dtype=torch.float32) for _ in range(layers)]
         self.v = [torch.empty((self.Tcap, N * H * W, C), device=device, dtype=torch.float32) for _ in range(layers)]
 
     def reset(self):
         self.len = 0
+        if self.pos is not None:
+            self.put_pos(0)
+
+    def put_pos(self, n):
+        """POS = n: one fill kernel, stream-ordered (never a memset node)"""
+        self.pos[ops.DECODE_POS:ops.DECODE_POS + 1].fill_(int(n))
+
+    def counters(self):
+        """{"pos", "tcap", "overflow", "steps"} of the device record (synchronises)"""
+        w = self.pos.tolist()
+        return {"pos": w[ops.DECODE_POS], "tcap": w[ops.DECODE_TCAP], "overflow": w[ops.DECODE_OVERFLOW], "steps": w[ops.DECODE_STEPS]}
+
+    def check(self):
+        """Read the device record (synchronises): RuntimeError if a step was ever refused on the device or the device's position
+        left the host's mirror."""
+        if self.pos is None:
+            return
+        c = self.counters()
+        if c["overflow"] or c["pos"] != self.len:
+            raise RuntimeError("FARCache: the device position record disagrees with the host (POS %d, host %d, %d refused steps)"
+                               % (c["pos"], self.len, c["overflow"]))
 
     def nbytes(self):
         return sum(t.numel() * 4 for t in self.k + self.v)

@@ -38,6 +38,7 @@ from .norm import (  # noqa: F401
 from .attention import (  # noqa: F401
     _winattn_workspace, _WinAttnFn, _WinAttnFn_apply, window_attention, _TAttnFn, _TAttnFn_apply, temporal_attention, KVGradAccum,
     _ProjAttnFn, _ProjAttnFn_apply, _proj_attention, proj_window_attention, proj_temporal_attention, proj_temporal_attention_step, _TSAttnFn,
+    DECODE_WORDS, DECODE_POS, DECODE_TCAP, DECODE_OVERFLOW, DECODE_STEPS, DECODE_MAXT, decode_begin, decode_advance,
     temporal_spatial_window_attention,
 )
 from .convffn import (  # noqa: F401

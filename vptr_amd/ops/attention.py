@@ -339,6 +339,25 @@ def proj_temporal_attention(q_in, k_in, v_in, Wq, bq, Wk, bk, Wv, bv, Nb, Tq, Tk
                            (int(Nb), int(Tq), int(Tk), int(HW), int(bool(causal))), nh, dropout_p, site, merge_v_grad, x_p16, o_p16, kv_acc, kv_out)
 
 
+DECODE_WORDS, DECODE_POS, DECODE_TCAP, DECODE_OVERFLOW, DECODE_STEPS = 16, 0, 1, 2, 3   # include/vptr_hip_decode.h
+DECODE_MAXT = 64
+
+
+def decode_begin(pos, tpos, tpos_cur):
+    """tpos_cur [C] = row POS of the [Tmax, C] temporal position table (vptr_decode_begin): once per decoding step"""
+    Tmax, C = tpos.shape
+    if tpos.dtype != torch.float32 or not tpos.is_contiguous() or tpos_cur.dtype != torch.float32 or tpos_cur.numel() != C or not tpos_cur.is_contiguous():
+        raise RuntimeError("decode_begin: tpos must be a contiguous fp32 [Tmax, C] table and tpos_cur a contiguous fp32 [C] buffer")
+    _lib.require_cuda(pos, tpos, tpos_cur)
+    check(lib.vptr_decode_begin(ptr(pos), ptr(tpos), ptr(tpos_cur), int(Tmax), int(C), stream()), "vptr_decode_begin")
+
+
+def decode_advance(pos):
+    """POS += 1, STEPS += 1 while POS < TCAP, else OVERFLOW += 1 (vptr_decode_advance)"""
+    _lib.require_cuda(pos)
+    check(lib.vptr_decode_advance(ptr(pos), stream()), "vptr_decode_advance")
+
+
 class _SlotPtr:
     """data_ptr() of one [rows, C] slot of a time-major cache, without building a view tensor per step"""
     __slots__ = ("p",)
@@ -350,12 +369,16 @@ class _SlotPtr:
         return self.p
 
 
-def proj_temporal_attention_step(xq, xv, Wq, bq, Wk, bk, Wv, bv, kcache, vcache, t, nh, x_p16=False, o_p16=False):
+def proj_temporal_attention_step(xq, xv, Wq, bq, Wk, bk, Wv, bv, kcache, vcache, t, nh, x_p16=False, o_p16=False, pos=None, staging=None):
     """One KV-cached decoding step of the causal temporal attention INCLUDING its q/k/v projections (inference only).
     xq = LayerNorm output + temporal-position row of frame t (queries and keys), xv = LayerNorm output (values), both [rows, C]
     (P16 tensors with x_p16); kcache, vcache [Tcap, rows, C] fp32, time-major.  The three projections run as one batched GEMM
     launch whose key / value outputs ARE slots kcache[t] / vcache[t] (contiguous slabs: no append copy); then one vptr_tattn_step
-    over slots 0 .. t.  Returns the [rows, C] heads before out_proj (a P16 tensor with o_p16)."""
+    over slots 0 .. t.  Returns the [rows, C] heads before out_proj (a P16 tensor with o_p16).
+
+    pos: the int32 position record of include/vptr_hip_decode.h.  The frame index is then the record's POS word, read on the device (`t`
+    is unused, so the launches are the same for every frame and can be captured once): the projections write the fixed buffers
+    staging = (k, v), both [rows, C] fp32, and vptr_tattn_step_pos appends them to slot POS while it attends over slots 0 .. POS."""
     if torch.is_grad_enabled() and any(a is not None and a.requires_grad for a in (xq, xv, Wq, bq, Wk, bk, Wv, bv, kcache, vcache)):
         raise RuntimeError("proj_temporal_attention_step is inference-only: call it under torch.no_grad()")
     _lib.require_cuda(xq, xv, Wq, kcache, vcache)
@@ -363,12 +386,24 @@ def proj_temporal_attention_step(xq, xv, Wq, bq, Wk, bk, Wv, bv, kcache, vcache,
     Wq, Wk, Wv = _c(Wq), _c(Wk), _c(Wv)
     M, K = xq.shape
     N = Wq.shape[0]
-    t = int(t)
+    t = int(t) if pos is None else -1
     for c in (kcache, vcache):
         if c.dtype != torch.float32 or c.dim() != 3 or tuple(c.shape[1:]) != (M, N) or not c.is_contiguous():
             raise RuntimeError("proj_temporal_attention_step: the caches must be contiguous fp32 [Tcap, %d, %d] tensors" % (M, N))
     Tcap = kcache.shape[0]
-    if vcache.shape[0] != Tcap or not 0 <= t < Tcap:
+    if pos is not None:
+        if pos.dtype != torch.int32 or pos.numel() != DECODE_WORDS or not pos.is_contiguous() or pos.device != kcache.device:
+            raise RuntimeError("proj_temporal_attention_step: pos must be the %d-word int32 position record on the caches' device" % DECODE_WORDS)
+        if staging is None or len(staging) != 2:
+            raise RuntimeError("proj_temporal_attention_step: a position record needs staging = (k, v)")
+        for c in staging:
+            if c.dtype != torch.float32 or tuple(c.shape) != (M, N) or not c.is_contiguous() or c.device != kcache.device:
+                raise RuntimeError("proj_temporal_attention_step: the staging buffers must be contiguous fp32 [%d, %d] tensors" % (M, N))
+        if vcache.shape[0] != Tcap:
+            raise RuntimeError("proj_temporal_attention_step: key and value caches differ in capacity")
+    elif staging is not None:
+        raise RuntimeError("proj_temporal_attention_step: staging buffers without a position record")
+    elif vcache.shape[0] != Tcap or not 0 <= t < Tcap:
         raise RuntimeError("proj_temporal_attention_step: slot %d outside a cache of %d frames" % (t, Tcap))
     if xv.shape != xq.shape:
         raise RuntimeError("proj_temporal_attention_step: xq and xv differ in shape")
@@ -377,7 +412,7 @@ def proj_temporal_attention_step(xq, xv, Wq, bq, Wk, bk, Wv, bv, kcache, vcache,
     if (x_p16 or o_p16) and not use:
         raise RuntimeError("attention: P16 operands need the embedding width to be a multiple of 16 (got %d)" % K)
     q = torch.empty((M, N), device=xq.device, dtype=torch.float32)
-    kt, vt = _SlotPtr(kcache, t), _SlotPtr(vcache, t)
+    kt, vt = staging if pos is not None else (_SlotPtr(kcache, t), _SlotPtr(vcache, t))
     if use:
         if not x_p16:
             same = xv is xq
@@ -391,6 +426,10 @@ def proj_temporal_attention_step(xq, xv, Wq, bq, Wk, bk, Wv, bv, kcache, vcache,
     else:
         gemm_raw(xq, Wq, q, M, N, K, 0, 0, bias=bq, alpha=alpha, batch_extra=[(xq, Wk, kt, bk, 1.0), (xv, Wv, vt, bv, 1.0)])
     o = torch.empty_like(q)
+    if pos is not None:
+        check(lib.vptr_tattn_step_pos(ptr(q), ptr(kt), ptr(vt), ptr(kcache), ptr(vcache), ptr(o), ptr(pos), M, Tcap, N, int(nh), int(bool(o_p16)),
+                                      stream()), "vptr_tattn_step_pos")
+        return o
     check(lib.vptr_tattn_step(ptr(q), ptr(kcache), ptr(vcache), ptr(o), M, t + 1, Tcap, N, int(nh), int(bool(o_p16)), stream()),
           "vptr_tattn_step")
     return o

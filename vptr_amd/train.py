@@ -1441,12 +1441,24 @@ class FARTrainer(NARTrainer):
         return l_gdl + l_point, {"T_GDL": l_gdl, "T_MSE": l_mse, "T_L1": l_l1}
 
     @torch.no_grad()
-    def predict(self, past, num_pred, kv_cache=False, weights="raw"):
-        """Autoregressive test-phase rollout (train_FAR.py:103-125): see vptr_amd.inference.far_rollout (kv_cache: its KV-cached path).
-        weights="ema": inside `ema_weights()`."""
-        from .inference import far_rollout
+    def predict(self, past, num_pred, kv_cache=False, weights="raw", graph=False, mode="train"):
+        """Autoregressive test-phase rollout (train_FAR.py:103-125): see vptr_amd.inference.far_rollout (kv_cache: its KV-cached path;
+        mode: its 'train' / 'RIP' / 'RIL').  weights="ema": inside `ema_weights()`.
+        graph=True (with kv_cache=True, else ValueError): the cached steps replay one captured hipGraph; the trainer keeps one
+        `CachedDecoder` per (batch size, mode), captured at its first use.  The graph reads the parameter slab by address, so it follows
+        `step()` and the EMA swap."""
+        from .inference import CachedDecoder, far_rollout
+        if graph and not kv_cache:
+            raise ValueError("far_rollout: graph=True replays the KV-cached step; it needs kv_cache=True")
         with self._weights(weights):
-            return far_rollout(self.enc, self.dec, self.T, past, num_pred, kv_cache=kv_cache)
+            if graph:
+                self.T.eval()
+                key = (int(past.shape[0]), mode)
+                decoders = self.__dict__.setdefault("_decoders", {})
+                if key not in decoders:
+                    decoders[key] = CachedDecoder(self.enc, self.dec, self.T, key[0], mode)
+                graph = decoders[key]
+            return far_rollout(self.enc, self.dec, self.T, past, num_pred, mode=mode, kv_cache=kv_cache, graph=graph)
 
     rollout = predict
 
